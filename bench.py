@@ -6,7 +6,7 @@ reference LR schedule, fp32 compute, synthetic MNIST-shaped data and random
 init, data parallel over N GPUs with a per-step gradient all-reduce (RCCL
 over xGMI, overlapped with backward).  Weak scaling: global batch = 64 * N.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--full] [--dump-outputs DIR]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N \
         --master-addr 127.0.0.1 --master-port P bench.py --gpus N --steps K --warmup W
 
@@ -29,6 +29,14 @@ after the eval passes on one box, final round-4 build; steady state 84).  With N
 sync schedule is autotuned first (real training steps, reported), and
 after the run every rank's weights are checksummed: replicas that differ
 fail the run (replicas_identical in the JSON).
+
+A plain run stops there.  --full adds what the headline figure does not
+need: the untimed accuracy run (MNIST: the rest of the reference's 2 epochs)
+and the test-set evaluation (final_test_accuracy; --no-eval leaves them out
+again).  --dump-outputs DIR writes the state the last timed step left
+(params, momentum, gradients, loss) as DIR/<name>.npy; the data and the
+initial weights come from the seed, so two builds run with the same
+arguments can be compared array for array.
 """
 
 from __future__ import annotations
@@ -60,6 +68,13 @@ def parse(argv=None):
     ap.add_argument("--no-graph", action="store_true")
     ap.add_argument("--backend", default="auto", choices=("auto", "native", "torch"))
     ap.add_argument("--no-eval", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also run the accuracy run (MNIST: the rest of "
+                         "the reference's 2 epochs, untimed) and the test-set evaluation "
+                         "(final_test_accuracy); a plain run only times the steps")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps write what they left (params, momentum, the "
+                         "last step's grads and loss) as DIR/<name>.npy")
     ap.add_argument("--sync-schedule", default="auto",
                     choices=("auto", "buckets", "sharded", "split", "factors", "serial", "defer",
                              "xgmi", "xgmi-step", "xgmi-fac"))
@@ -199,6 +214,37 @@ def prewarm(eng, x, y, ms: float) -> float:
     while 1000.0 * (time.perf_counter() - t0) < ms:
         eng.evaluate(xs, ys)
     return round(1000.0 * (time.perf_counter() - t0), 1)
+
+
+DUMP_BYTES = 48 << 20  # --dump-outputs: upper bound of all files together (fp32 data)
+
+
+def dump_outputs(eng, path: str) -> dict:
+    """Writes what a caller of eng.train() holds after the last timed step
+    as `path`/<name>.npy (float32; the loss as float64): the flat params,
+    momentum and last-step gradient buffers, the non-trained model state
+    (BatchNorm running statistics) and the last step's loss.  A flat buffer
+    larger than a third of DUMP_BYTES is stored as a fixed sample: the
+    elements at the sorted indices drawn once from numpy's default_rng(0), so
+    two builds sample the same elements.  Returns {name: stored elements}."""
+    import numpy as np
+
+    os.makedirs(path, exist_ok=True)
+    arrays = {"params": eng.params, "momentum": eng.mom, "grads": eng.grads}
+    cap = DUMP_BYTES // 4 // len(arrays)  # elements of a flat buffer (the state is small)
+    for name, t in eng.extra_state().items():
+        arrays["state." + name.replace("/", ".")] = t
+    stored = {}
+    for name, t in arrays.items():
+        v = t.detach().to(torch.float32).reshape(-1).cpu().numpy()
+        if v.size > cap:
+            idx = np.sort(np.random.default_rng(0).choice(v.size, cap, replace=False))
+            v = v[idx]
+        np.save(os.path.join(path, name + ".npy"), np.ascontiguousarray(v, np.float32))
+        stored[name] = int(v.size)
+    np.save(os.path.join(path, "loss.npy"), np.array([eng.loss_value()], np.float64))
+    stored["loss"] = 1
+    return stored
 
 
 def main(argv=None) -> int:
@@ -362,8 +408,18 @@ def run(a, di, device, wd) -> int:
     dt = D.allreduce_max_host(t1 - t0)
     if N > 1:  # every rank stops when any rank's xGMI barrier timed out
         check_health("timed steps", comm, eng)
+    dumped = None
+    if a.dump_outputs:
+        # the state the timed steps left, before anything else trains on it
+        # (sharded optimizers first make the momentum whole: collective)
+        if hasattr(eng, "sync_optimizer_state"):
+            eng.sync_optimizer_state()
+        sync()
+        if di.rank == 0:
+            dumped = dump_outputs(eng, a.dump_outputs)
+        D.barrier()
     err = float("nan")
-    if not a.no_eval:
+    if a.full and not a.no_eval:
         # accuracy of the reference's full run: MNIST trains `epochs` local
         # epochs (mpipy.py:79, 2 x N_local // 64 steps per rank); the timed
         # steps count towards it and the rest run untimed here (fast: the
@@ -448,6 +504,8 @@ def run(a, di, device, wd) -> int:
             "final_test_accuracy": None if err != err else round(100.0 - err, 3),
             "test_eval_after_steps": int(eng.step),
             "test_rows": int(test_x.shape[0]) * N,
+            "full": bool(a.full),
+            "outputs": dumped,  # --dump-outputs: {name: stored elements}
         }
         print(json.dumps(out))
         sys.stdout.flush()

@@ -56,7 +56,7 @@ def test_bench_two_ranks_shared_gpu(cuda_dev, model, dtype, extra):
     the driver's N > 1 runs do apart from the communicator."""
     steps = 10 if model == "resnet18" else 30
     out = _run([sys.executable, "bench.py", "--gpus", "2", "--comm", "shm", "--model", model,
-                "--dtype", dtype, "--steps", str(steps), "--warmup", "5"] + extra)
+                "--dtype", dtype, "--steps", str(steps), "--warmup", "5", "--full"] + extra)
     lines = _json_lines(out)
     assert len(lines) == 1, out
     j = lines[0]
@@ -89,7 +89,7 @@ def test_bench_two_ranks_xgmi_peer_to_peer(cuda_dev, model, dtype):
     MNIST tunes its fused sync + SGD launch against the plain peer-to-peer
     all-reduce, and the replicas must end bit-identical."""
     out = _run([sys.executable, "bench.py", "--gpus", "2", "--comm", "xgmi", "--model", model,
-                "--dtype", dtype, "--steps", "30", "--warmup", "5"])
+                "--dtype", dtype, "--steps", "30", "--warmup", "5", "--full"])
     lines = _json_lines(out)
     assert len(lines) == 1, out
     c = lines[0]["config"]
