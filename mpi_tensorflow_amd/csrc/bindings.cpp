@@ -185,6 +185,63 @@ PYBIND11_MODULE(_C, m) {
                                       P<unsigned long long>(prof));
     check_launch();
   });
+  // Compact Winograd backward (tests, labs).  dY2 is dense (dy2) or, with
+  // dy2 == 0, the pooled gradient dp2 [B][7][7][64] + its argmax codes idx2;
+  // a1 == 0 takes the ReLU1 mask from a1pf, da1m == 0 skips the dA1 store.
+  k.def("fc1_bwd_dp2", [](uintptr_t a2, uintptr_t idx2, uintptr_t dh, uintptr_t hd, uintptr_t dlog,
+                          uintptr_t w1, int batch, uintptr_t g_w3, uintptr_t g_b3, uintptr_t g_w4,
+                          uintptr_t g_b4, uintptr_t dp2, uintptr_t s, int roles) {
+    mnist::launch_fc1_bwd(P<const float>(a2), P<const uint8_t>(idx2), P<const float>(dh),
+                          P<const float>(hd), P<const float>(dlog), P<const float>(w1), batch,
+                          P<float>(g_w3), P<float>(g_b3), P<float>(g_w4), P<float>(g_b4), nullptr,
+                          nullptr, S(s), roles, P<float>(dp2));
+    check_launch();
+  }, py::arg("a2"), py::arg("idx2"), py::arg("dh"), py::arg("hd"), py::arg("dlog"), py::arg("w1"),
+     py::arg("batch"), py::arg("g_w3"), py::arg("g_b3"), py::arg("g_w4"), py::arg("g_b4"),
+     py::arg("dp2"), py::arg("stream"), py::arg("roles") = 7);
+  // bwd-data with the conv1 filter-gradient epilogue (part1); prof as
+  // conv2_bwd_data_wino_prof
+  k.def("conv2_bwd_data_wino_c1", [](uintptr_t dy2, uintptr_t dp2, uintptr_t idx2, uintptr_t Ud,
+                                     uintptr_t a1, uintptr_t a1pf, int batch, uintptr_t da1m,
+                                     uintptr_t data, uintptr_t step, int n_local, uintptr_t idx1,
+                                     uintptr_t part1, uintptr_t s, uintptr_t prof) {
+    const mnist::C1FilterArgs c1{P<const float>(data), P<const long long>(step), n_local,
+                                 P<const float>(da1m), P<const uint8_t>(idx1), P<float>(part1)};
+    mnist::launch_conv2_bwd_data_wino(P<const float>(dy2), P<const float>(Ud), P<const float>(a1),
+                                      batch, P<float>(da1m), S(s), nullptr, &c1,
+                                      P<unsigned long long>(prof), P<const float>(dp2),
+                                      P<const uint8_t>(idx2), P<const float>(a1pf));
+    check_launch();
+  }, py::arg("dy2"), py::arg("dp2"), py::arg("idx2"), py::arg("Ud"), py::arg("a1"),
+     py::arg("a1pf"), py::arg("batch"), py::arg("da1m"), py::arg("data"), py::arg("step"),
+     py::arg("n_local"), py::arg("idx1"), py::arg("part1"), py::arg("s"), py::arg("prof") = 0);
+  k.def("conv2_bwd_filter_wino_dp2", [](uintptr_t a1p, uintptr_t dp2, uintptr_t idx2, int batch,
+                                        uintptr_t part2, uintptr_t s, uintptr_t prof) {
+    if (prof)
+      mnist::launch_conv2_bwd_filter_wino_prof(P<const float>(a1p), nullptr, batch,
+                                               P<float>(part2), P<unsigned long long>(prof), S(s),
+                                               P<const float>(dp2), P<const uint8_t>(idx2));
+    else
+      mnist::launch_conv2_bwd_filter_wino(P<const float>(a1p), nullptr, batch, P<float>(part2),
+                                          S(s), nullptr, P<const float>(dp2),
+                                          P<const uint8_t>(idx2));
+    check_launch();
+  }, py::arg("a1p"), py::arg("dp2"), py::arg("idx2"), py::arg("batch"), py::arg("part2"),
+     py::arg("s"), py::arg("prof") = 0);
+  // both roles in one launch (the executor's single-rank form)
+  k.def("conv2_bwd_wino", [](uintptr_t Ud, uintptr_t a1, uintptr_t a1p, uintptr_t dy2,
+                             uintptr_t dp2, uintptr_t idx2, int batch, uintptr_t da1m,
+                             uintptr_t part2, uintptr_t data, uintptr_t step, int n_local,
+                             uintptr_t idx1, uintptr_t part1, uintptr_t s) {
+    const mnist::C1FilterArgs c1{P<const float>(data), P<const long long>(step), n_local,
+                                 P<const float>(da1m), P<const uint8_t>(idx1), P<float>(part1)};
+    mnist::launch_conv2_bwd_wino(P<const float>(Ud), P<const float>(a1), P<const float>(a1p),
+                                 P<const float>(dy2), batch, P<float>(da1m), P<float>(part2), S(s),
+                                 &c1, nullptr, P<const float>(dp2), P<const uint8_t>(idx2));
+    check_launch();
+  }, py::arg("Ud"), py::arg("a1"), py::arg("a1p"), py::arg("dy2"), py::arg("dp2"),
+     py::arg("idx2"), py::arg("batch"), py::arg("da1m"), py::arg("part2"), py::arg("data"),
+     py::arg("step"), py::arg("n_local"), py::arg("idx1"), py::arg("part1"), py::arg("s"));
   k.def("fc1_train_splits", &mnist::fc1_train_splits);
   k.def("conv2_filter_splits", &mnist::conv2_filter_splits);
   k.def("conv1_filter_blocks", [](int batch, int split) {
@@ -658,7 +715,7 @@ PYBIND11_MODULE(_C, m) {
                                   RW(a1p) RW(a1t) RW(a2h) RW(a2t) RW(dy2p) RW(dy2t) RW(dh16)
                                       RW(dht16) RW(w1b) RW(w1t) RW(w2tb) RW(w2b) RW(a2_all)
                                           RW(dh_all) RW(hd_all) RW(dlog_all) RW(fac_ranks)
-                                              RW(wino) RW(wino_u) RW(wino_ud) RW(a2ft);
+                                              RW(wino) RW(wino_u) RW(wino_ud) RW(a2ft) RW(dp2);
 #undef RW
 
   py::class_<Collective>(m, "Collective")

@@ -95,7 +95,14 @@ void launch_conv2_fwd_wino(const float* a1, int batch, const float* w2, const fl
 void launch_conv2_bwd_data_wino(const float* dy2, const float* Ud, const float* a1, int batch,
                                 float* da1m, hipStream_t s, const FcSgdArgs* fc_sgd = nullptr,
                                 const C1FilterArgs* c1 = nullptr,
-                                unsigned long long* prof = nullptr);
+                                unsigned long long* prof = nullptr, const float* dp2 = nullptr,
+                                const uint8_t* idx2 = nullptr, const float* a1pf = nullptr);
+// The Winograd backward launchers take dY2 dense (dy2) or, with dy2 == nullptr,
+// compact: dp2 [B][7][7][64] (launch_fc1_bwd's dp2 form) + its argmax codes
+// idx2 - the same results bit for bit from a quarter of the loads.
+// bwd-data: a1 == nullptr reads the ReLU1 mask operand from the zero-bordered
+// a1pf instead; da1m == nullptr skips the dA1 store (only with c1->part1, whose
+// conv1 filter gradient is formed from registers).
 // Both Winograd conv2 backward products in one launch: bwd-data (as
 // launch_conv2_bwd_data_wino, dy2 / Ud / a1 -> da1m, + the conv1 filter-grad
 // partials c1; no FC SGD) and the filter gradient (as
@@ -106,7 +113,8 @@ void launch_conv2_bwd_data_wino(const float* dy2, const float* Ud, const float* 
 struct XgmiStepArgs;
 void launch_conv2_bwd_wino(const float* Ud, const float* a1, const float* a1p, const float* dy2,
                            int batch, float* da1m, float* part2, hipStream_t s,
-                           const C1FilterArgs* c1 = nullptr, const XgmiStepArgs* xfc = nullptr);
+                           const C1FilterArgs* c1 = nullptr, const XgmiStepArgs* xfc = nullptr,
+                           const float* dp2 = nullptr, const uint8_t* idx2 = nullptr);
 int fc1_train_splits();
 void launch_fc1_fwd_train(const float* a2, const float* w, int batch, float* part, hipStream_t s);
 // fc1 train forward over the feature-major a2t [3136][batch] (batch % 32 ==
@@ -129,8 +137,12 @@ void launch_fc_head_eval(const float* h, const float* w4, const float* b4, const
 void launch_fc1_bwd(const float* a2, const uint8_t* idx2, const float* dh, const float* hd,
                     const float* dlog, const float* w1, int batch, float* g_w3, float* g_b3,
                     float* g_w4, float* g_b4, float* dy2, float* dy2t, hipStream_t s,
-                    int roles = 7);  // roles: bit 0 dX, bit 1 dW1, bit 2 small grads
+                    int roles = 7,   // roles: bit 0 dX, bit 1 dW1, bit 2 small grads
                                      // (roles == 1: a dX-only grid, SCHED_FACTORS)
+                    float* dp2 = nullptr);
+// dy2 == nullptr: the dX role writes the compact form instead - dp2
+// [B][7][7][64], the ReLU2-masked pooled gradient at a2's flat index (one
+// 4-byte store per element, not four); its argmax codes are idx2
 // FC weight / bias grads over `rows` gathered rows (rank-major a2 [rows][3136],
 // dh / hd [rows][512], dlog [rows][10]); SCHED_FACTORS
 void launch_fc1_bwd_weights(const float* a2, const float* dh, const float* hd, const float* dlog,
@@ -147,10 +159,12 @@ void launch_conv2_bwd_filter(const float* a1p, const float* dy2, int batch, floa
 int conv2_wino_filter_groups(int batch);
 size_t part2_floats_wino(int batch);
 void launch_conv2_bwd_filter_wino(const float* a1p, const float* dy2, int batch, float* part2,
-                                  hipStream_t s, const C1FilterArgs* c1 = nullptr);
+                                  hipStream_t s, const C1FilterArgs* c1 = nullptr,
+                                  const float* dp2 = nullptr, const uint8_t* idx2 = nullptr);
 // phase timing of the above (s_memtime per wave, [blocks][waves][5]); labs only
 void launch_conv2_bwd_filter_wino_prof(const float* a1p, const float* dy2, int batch,
-                                       float* part2, unsigned long long* prof, hipStream_t s);
+                                       float* part2, unsigned long long* prof, hipStream_t s,
+                                       const float* dp2 = nullptr, const uint8_t* idx2 = nullptr);
 // L2-direct bwd-data (the one the executor uses): dy2t from launch_fc1_bwd,
 // w2t from launch_conv2_fwd; batch % 8 == 0
 void launch_conv2_bwd_data_l2(const float* dy2t, const float* w2t, const float* a1, int batch,
@@ -283,7 +297,7 @@ void launch_xgmi_fac_gather(const XgmiFacArgs& a, hipStream_t s);
 // factor gather as extra role blocks (the factors are final after the head)
 void launch_fc1_bwd_dx_fac_gather(const float* a2, const uint8_t* idx2, const float* dh,
                                   const float* w1, int batch, float* dy2, float* dy2t,
-                                  const XgmiFacArgs& f, hipStream_t s);
+                                  const XgmiFacArgs& f, hipStream_t s, float* dp2 = nullptr);
 // fc2 / bias grads (dW2, db2, db1) over `rows` gathered rows (the small role of
 // launch_fc1_bwd_weights alone)
 void launch_fc1_small_grads(const float* dh, const float* hd, const float* dlog, int rows,

@@ -452,7 +452,7 @@ __device__ __forceinline__ void fc1_bwd_dx(int L, const float* __restrict__ a2,
                                            const float* __restrict__ dh,
                                            const float* __restrict__ w1, int batch,
                                            float* __restrict__ dy2, float* __restrict__ dy2t,
-                                           float* smem) {
+                                           float* __restrict__ dp2, float* smem) {
   const int n_m = batch / 32;
   const int mt = L % n_m, nt = L / n_m;
   const int m0 = mt * 32, n0 = nt * 32;
@@ -522,6 +522,16 @@ __device__ __forceinline__ void fc1_bwd_dx(int L, const float* __restrict__ a2,
     float g = smem[k * 64 + lane] + smem[FC1DX_WAVE + k * 64 + lane] +
               smem[2 * FC1DX_WAVE + k * 64 + lane] + smem[3 * FC1DX_WAVE + k * 64 + lane];
     if (relu_in[j] <= 0.f) g = 0.f;  // ReLU2 inactive at the argmax
+    if (dy2 == nullptr) {
+      // compact form: the pooled gradient alone, at a2's flat index (its
+      // argmax code stays in idx2) - one 128-B line per half-wave instead of
+      // four 4-byte stores, three of them zeros.  The index is that of the
+      // relu_in load; formed again from a fresh lane id so the four offsets
+      // are not kept in registers across the products.
+      const int l2 = __builtin_amdgcn_mbcnt_hi(~0u, __builtin_amdgcn_mbcnt_lo(~0u, 0u));
+      dp2[(unsigned)((m0 + mfma32_row(k, l2)) * FC1_IN + n0 + (l2 & 31))] = g;
+      continue;
+    }
 #pragma unroll
     for (int dy = 0; dy < 2; ++dy) {
       const int y = 2 * py + dy, x = 2 * px;
@@ -637,9 +647,11 @@ __global__ __launch_bounds__(256) void fc1_bwd_kernel(
     const float* __restrict__ a2, const uint8_t* __restrict__ idx2, const float* __restrict__ dh,
     const float* __restrict__ hd, const float* __restrict__ dlog, const float* __restrict__ w1,
     int batch, float* __restrict__ g_w3, float* __restrict__ g_b3, float* __restrict__ g_w4,
-    float* __restrict__ g_b4, float* __restrict__ dy2, float* __restrict__ dy2t, int roles) {
+    float* __restrict__ g_b4, float* __restrict__ dy2, float* __restrict__ dy2t,
+    float* __restrict__ dp2, int roles) {
   // dy2: NHWC [n][14][14][64]; dy2t: channel-major, zero-bordered
-  // [n][64][18][MNIST32_T_LD] (its border is never written)
+  // [n][64][18][MNIST32_T_LD] (its border is never written); dy2 == nullptr:
+  // the compact dp2 [n][7][7][64] instead (fc1_bwd_dx)
   constexpr int S_DX = 4 * FC1DX_WAVE, S_SMALL = FC1_SMALL_SMEM;
   __shared__ float smem[S_DX > S_SMALL ? S_DX : S_SMALL];
   // the grid holds the blocks of the roles asked for, in the order dX, dW1,
@@ -648,7 +660,7 @@ __global__ __launch_bounds__(256) void fc1_bwd_kernel(
   const int n_dw = (roles & 2) ? FC1BWD_DW_BLOCKS : 0;
   const int L = xcd_remap(blockIdx.x, gridDim.x);
   if (L < n_dx)
-    fc1_bwd_dx(L, a2, idx2, dh, w1, batch, dy2, dy2t, smem);
+    fc1_bwd_dx(L, a2, idx2, dh, w1, batch, dy2, dy2t, dp2, smem);
   else if (L < n_dx + n_dw)
     fc1_bwd_dw(L - n_dx, a2, dh, batch, g_w3, threadIdx.x >> 6);
   else
@@ -848,7 +860,7 @@ __device__ __forceinline__ void halo_flush_owned(const C12In& c1, const float* x
     const float* s = xs + ((r + 2) * C2_XS_COLS + x + 2) * 33 + c;
     const float4 v = make_float4(s[0], s[1], s[2], s[3]);
     const size_t pi = ((size_t)(n * 14 + yo + r) * 14 + x) * 32 + c;
-    *reinterpret_cast<float4*>(c1.a1 + pi) = v;
+    if (c1.a1 != nullptr) *reinterpret_cast<float4*>(c1.a1 + pi) = v;
     *reinterpret_cast<float4*>(c1.a1pf + ((size_t)(n * 18 + yo + r + 2) * 18 + x + 2) * 32 + c) = v;
     *reinterpret_cast<uint32_t*>(c1.idx1 + pi) = *reinterpret_cast<const uint32_t*>(q1 + pix * 32 + c);
   }
@@ -1387,11 +1399,19 @@ constexpr int WD_SMEM = WV_FLOATS + WB_FLOATS;  // bwd-data body LDS (floats)
 // Block body (blk of nblk, threads 0 .. WNT - 1, smem: WD_SMEM floats): the
 // standalone kernel below, or the bwd-data role of the merged conv2 backward
 // launch
-template <bool PROF, bool FC = true>
+// COMPACT: dy2 is the compact dp2 [n][7][7][64] (the pooled gradient, fc1
+// backward's dy2 == nullptr form) with its argmax codes idx2: a band is 4
+// pooled rows (2 pg - 1 .. 2 pg + 2) x 7 x 32 channels, a quarter of the
+// dense band's loads, expanded into the same staged image.
+// a1 == nullptr: the ReLU1 mask operand comes from the zero-bordered a1pf
+// (same values at (y + 2, x + 2)); da1m == nullptr: dA1 is not stored (its
+// only reader, conv1_filter_unit, is not run when c1.part1 is formed here).
+template <bool PROF, bool FC = true, bool COMPACT = false>
 __device__ __forceinline__ void bwd_data_wino_block(
-    int blk, int nblk, const float* __restrict__ dy2, const float* __restrict__ Ud,
-    const float* __restrict__ a1, int batch, float* __restrict__ da1m, const FcSgd& sgd,
-    const C1Filter& c1, unsigned long long* __restrict__ prof, float* smem) {
+    int blk, int nblk, const float* __restrict__ dy2, const uint8_t* __restrict__ idx2,
+    const float* __restrict__ Ud, const float* __restrict__ a1, const float* __restrict__ a1pf,
+    int batch, float* __restrict__ da1m, const FcSgd& sgd, const C1Filter& c1,
+    unsigned long long* __restrict__ prof, float* smem) {
   // PROF (labs): s_memtime per wave -> prof[block][wave][7]: start, half 0
   // transform / products, half 1 transform / products, dA1 written, end
   unsigned long long stamp[7];
@@ -1427,28 +1447,69 @@ __device__ __forceinline__ void bwd_data_wino_block(
   const bool it_ok = it_t < 14 && it_tr < 7;
   const int y0b = 4 * pg - 2;  // image row of band row 0
   constexpr int BAND4 = WB_ROWS * 14 * 8, BJ = (BAND4 + WNT - 1) / WNT;  // 896 float4, 2 / thread
-  float4 bq[2][BJ];
+  // COMPACT: 4 pooled rows x 7 x 8 float4 = 224 (value, 4 codes) items per
+  // half; thread (dy, item) of 2 x 224 expands pixel row 2 pr + dy of its
+  // item's four channels (both dy threads load the same 16 + 4 bytes)
+  constexpr int CB4 = 4 * 7 * 8;
+  constexpr int BQ = COMPACT ? 1 : BJ;
+  float4 bq[2][BQ];
+  uint32_t bk[2] = {0u, 0u};
+  // the thread's item in one register for stage(): the float offset of its
+  // first cell in SB, bit 16 its dy, bit 17 a pooled row outside the image
+  // (stages zeros); -1: no item
+  int cb_item = -1;
 #pragma unroll
-  for (int hh = 0; hh < 2; ++hh)
+  for (int hh = 0; hh < 2; ++hh) {
+    if constexpr (COMPACT) {
+      const int cb_dy = tid >= CB4 ? 1 : 0, cb_f = min(tid - cb_dy * CB4, CB4 - 1);
+      const int cb_c4 = cb_f & 7, cb_pr = (cb_f >> 3) / 7, cb_px = (cb_f >> 3) % 7;
+      const int cb_py = 2 * pg - 1 + cb_pr;  // pooled row of the item
+      if (tid < 2 * CB4)
+        cb_item = (((4 * cb_c4) * WB_ROWS + 2 * cb_pr + cb_dy) * WB_COLS + 2 * cb_px + 2) |
+                  (cb_dy << 16) | ((cb_py >= 0 && cb_py < 7) ? 0 : 1 << 17);
+      const size_t i = (size_t)n * FC1_IN + (min(max(cb_py, 0), 6) * 7 + cb_px) * 64 + 32 * hh +
+                       4 * cb_c4;
+      bq[hh][0] = *reinterpret_cast<const float4*>(dy2 + i);
+      bk[hh] = *reinterpret_cast<const uint32_t*>(idx2 + i);
+    } else {
 #pragma unroll
-    for (int j = 0; j < BJ; ++j) {
-      const int f = min(tid + WNT * j, BAND4 - 1), c4 = f & 7, pix = f >> 3;
-      const int y = min(max(y0b + pix / 14, 0), 13), x = pix % 14;
-      bq[hh][j] = *reinterpret_cast<const float4*>(dy2 + ((size_t)(n * 14 + y) * 14 + x) * 64 +
-                                                   32 * hh + 4 * c4);
+      for (int j = 0; j < BJ; ++j) {
+        const int f = min(tid + WNT * j, BAND4 - 1), c4 = f & 7, pix = f >> 3;
+        const int y = min(max(y0b + pix / 14, 0), 13), x = pix % 14;
+        bq[hh][j] = *reinterpret_cast<const float4*>(dy2 + ((size_t)(n * 14 + y) * 14 + x) * 64 +
+                                                     32 * hh + 4 * c4);
+      }
     }
+  }
   auto stage = [&](int hh) {  // band hh -> SB (zero borders); no barrier
+    if constexpr (COMPACT) {
+      if (cb_item >= 0) {
+        const bool ok = (cb_item & (1 << 17)) == 0;
+        const int cb_dy = (cb_item >> 16) & 1;
+        const float vq[4] = {bq[hh][0].x, bq[hh][0].y, bq[hh][0].z, bq[hh][0].w};
+        float* d = SB + (cb_item & 0xffff);
 #pragma unroll
-    for (int j = 0; j < BJ; ++j) {
-      const int f = tid + WNT * j;
-      if (f < BAND4) {
-        const int c4 = f & 7, pix = f >> 3, r = pix / 14, x = pix % 14;
-        const bool ok = y0b + r >= 0 && y0b + r < 14;
-        float* d = SB + ((4 * c4) * WB_ROWS + r) * WB_COLS + x + 2;
-        d[0] = ok ? bq[hh][j].x : 0.f;
-        d[WB_ROWS * WB_COLS] = ok ? bq[hh][j].y : 0.f;
-        d[2 * WB_ROWS * WB_COLS] = ok ? bq[hh][j].z : 0.f;
-        d[3 * WB_ROWS * WB_COLS] = ok ? bq[hh][j].w : 0.f;
+        for (int c = 0; c < 4; ++c) {
+          // the value at its argmax position (code = 2 dy + dx), zeros elsewhere
+          const int code = (bk[hh] >> (8 * c)) & 3;
+          const float v = (ok && (code >> 1) == cb_dy) ? vq[c] : 0.f;
+          *reinterpret_cast<float2*>(d + c * WB_ROWS * WB_COLS) =
+              (code & 1) ? make_float2(0.f, v) : make_float2(v, 0.f);
+        }
+      }
+    } else {
+#pragma unroll
+      for (int j = 0; j < BJ; ++j) {
+        const int f = tid + WNT * j;
+        if (f < BAND4) {
+          const int c4 = f & 7, pix = f >> 3, r = pix / 14, x = pix % 14;
+          const bool ok = y0b + r >= 0 && y0b + r < 14;
+          float* d = SB + ((4 * c4) * WB_ROWS + r) * WB_COLS + x + 2;
+          d[0] = ok ? bq[hh][j].x : 0.f;
+          d[WB_ROWS * WB_COLS] = ok ? bq[hh][j].y : 0.f;
+          d[2 * WB_ROWS * WB_COLS] = ok ? bq[hh][j].z : 0.f;
+          d[3 * WB_ROWS * WB_COLS] = ok ? bq[hh][j].w : 0.f;
+        }
       }
     }
     // the 2 + 2 zero columns of every (channel, row): 32 x 8 x 4 = 1024 cells
@@ -1544,9 +1605,14 @@ __device__ __forceinline__ void bwd_data_wino_block(
   // the dA1 stores below would wait for them: vmcnt counts both)
   float a1v[4] = {0.f, 0.f, 0.f, 0.f};
   if (own) {
+    // a1 [n][14][14][32], or its zero-bordered copy a1pf [n][18][18][32]
+    const bool pf = COMPACT || a1 == nullptr;
+    const float* am = pf ? a1pf : a1;
+    const int ms = pf ? 18 : 14, mo = pf ? 2 : 0;
 #pragma unroll
     for (int o = 0; o < 4; ++o)
-      a1v[o] = a1[((size_t)(n * 14 + 2 * tr + (o >> 1)) * 14 + 2 * tc + (o & 1)) * 32 + ci];
+      a1v[o] = am[((size_t)(n * ms + 2 * tr + (o >> 1) + mo) * ms + 2 * tc + (o & 1) + mo) * 32 +
+                  ci];
   }
   if (do_c1) {
     const long long off = batch_offset_dev(c1.step, c1.n_local, batch);
@@ -1574,7 +1640,7 @@ __device__ __forceinline__ void bwd_data_wino_block(
       const size_t oi =
           ((size_t)(n * 14 + 2 * tr + (o >> 1)) * 14 + 2 * tc + (o & 1)) * 32 + ci;
       g1[o] = a1v[o] > 0.f ? sum : 0.f;
-      da1m[oi] = g1[o];
+      if (da1m != nullptr) da1m[oi] = g1[o];
     }
   }
   if constexpr (PROF) stamp[5] = __builtin_amdgcn_s_memtime();
@@ -1620,13 +1686,15 @@ __device__ __forceinline__ void bwd_data_wino_block(
   fc_sgd_tail();
 }
 
-template <bool PROF = false>
+template <bool PROF = false, bool COMPACT = false>
 __global__ __launch_bounds__(WNT) void conv2_bwd_data_wino_kernel(
-    const float* __restrict__ dy2, const float* __restrict__ Ud, const float* __restrict__ a1,
-    int batch, float* __restrict__ da1m, const FcSgd sgd, const C1Filter c1,
+    const float* __restrict__ dy2, const uint8_t* __restrict__ idx2, const float* __restrict__ Ud,
+    const float* __restrict__ a1, const float* __restrict__ a1pf, int batch,
+    float* __restrict__ da1m, const FcSgd sgd, const C1Filter c1,
     unsigned long long* __restrict__ prof = nullptr) {
   __shared__ float smem[WD_SMEM];
-  bwd_data_wino_block<PROF>(blockIdx.x, gridDim.x, dy2, Ud, a1, batch, da1m, sgd, c1, prof, smem);
+  bwd_data_wino_block<PROF, true, COMPACT>(blockIdx.x, gridDim.x, dy2, idx2, Ud, a1, a1pf, batch,
+                                           da1m, sgd, c1, prof, smem);
 }
 
 // ------------------------------------------ Winograd conv2 bwd-filter ----
@@ -1726,11 +1794,17 @@ __device__ __forceinline__ void wino_wgrad_row(const float* __restrict__ xs,
 // of the merged conv2 backward launch (blk = block index - bwd-data blocks, a
 // multiple of 8: the XCD-aware group mapping is kept)
 constexpr int WF_SMEM_ALL = WF_SMEM > c1f_smem<1, WF_NT / 64>() ? WF_SMEM : c1f_smem<1, WF_NT / 64>();
-template <bool PROF>
+// COMPACT: dy2 is the compact dp2 [n][7][7][64] with its argmax codes idx2 (a
+// quarter of the slice loads); the staging expands it into the same dense
+// LDS slices, so everything after it - and every sum - is the dense form's.
+// (Keeping the slices compact in LDS - one value + a 2-bit code per tile, the
+// row transform as a selected kAT coefficient - changed how the compiler
+// contracts the main loop's window transform: part2 differed in the last bit.)
+template <bool PROF, bool COMPACT = false>
 __device__ __forceinline__ void bwd_filter_wino_block(
     int blk, int batch, const float* __restrict__ a1p, const float* __restrict__ dy2,
-    float* __restrict__ part2, float* __restrict__ part_db2, int nwg, const C1Filter& c1,
-    unsigned long long* __restrict__ prof, float* smem) {
+    const uint8_t* __restrict__ idx2, float* __restrict__ part2, float* __restrict__ part_db2,
+    int nwg, const C1Filter& c1, unsigned long long* __restrict__ prof, float* smem) {
   unsigned long long stamp[5];
   if constexpr (PROF) stamp[0] = __builtin_amdgcn_s_memtime();
   if (blk >= nwg) {  // conv1 filter-grad role (its dA1 is final)
@@ -1758,8 +1832,13 @@ __device__ __forceinline__ void bwd_filter_wino_block(
   // 1. slices -> LDS (every load issued before the first store)
   {
     constexpr int NX = WF_IMG * 324 * 4, ND = WF_IMG * 196 * 4;  // float4s
-    constexpr int PX = (NX + WF_NT - 1) / WF_NT, PD = (ND + WF_NT - 1) / WF_NT;
+    constexpr int PX = (NX + WF_NT - 1) / WF_NT;
+    constexpr int PD = COMPACT ? 1 : (ND + WF_NT - 1) / WF_NT;
+    // COMPACT: threads 0 .. NC - 1 one float4 of values + its 4 codes each
+    constexpr int NC = WF_IMG * 49 * 4;
+    static_assert(NC <= WF_NT, "one compact item per thread");
     float4 vx[PX], vd[PD];
+    uint32_t vk = 0u;
 #pragma unroll
     for (int j = 0; j < PX; ++j) {
       const int i = min(tid + j * WF_NT, NX - 1), pix = i >> 2, img = pix / 324;
@@ -1767,12 +1846,20 @@ __device__ __forceinline__ void bwd_filter_wino_block(
       vx[j] = *reinterpret_cast<const float4*>(
           a1p + ((size_t)n * 324 + (pix - 324 * img)) * 32 + ci_t * 16 + 4 * (i & 3));
     }
-#pragma unroll
-    for (int j = 0; j < PD; ++j) {
-      const int i = min(tid + j * WF_NT, ND - 1), pix = i >> 2, img = pix / 196;
+    if constexpr (COMPACT) {
+      const int i = min(tid, NC - 1), pix = i >> 2, img = pix / 49;
       const int n = min(n0 + img, batch - 1);
-      vd[j] = *reinterpret_cast<const float4*>(
-          dy2 + ((size_t)n * 196 + (pix - 196 * img)) * 64 + co_t * 16 + 4 * (i & 3));
+      const size_t gi = ((size_t)n * 49 + (pix - 49 * img)) * 64 + co_t * 16 + 4 * (i & 3);
+      vd[0] = *reinterpret_cast<const float4*>(dy2 + gi);
+      vk = *reinterpret_cast<const uint32_t*>(idx2 + gi);
+    } else {
+#pragma unroll
+      for (int j = 0; j < PD; ++j) {
+        const int i = min(tid + j * WF_NT, ND - 1), pix = i >> 2, img = pix / 196;
+        const int n = min(n0 + img, batch - 1);
+        vd[j] = *reinterpret_cast<const float4*>(
+            dy2 + ((size_t)n * 196 + (pix - 196 * img)) * 64 + co_t * 16 + 4 * (i & 3));
+      }
     }
 #pragma unroll
     for (int j = 0; j < PX; ++j) {
@@ -1787,17 +1874,38 @@ __device__ __forceinline__ void bwd_filter_wino_block(
         d[3 * WF_XLD] = vx[j].w;
       }
     }
+    if constexpr (COMPACT) {
+      if (tid < NC) {
+        const int pix = tid >> 2, img = pix / 49, pp = pix - 49 * img, ty = pp / 7;
+        const int tx = pp - 7 * ty, c0 = 4 * (tid & 3);
+        const float vq[4] = {vd[0].x, vd[0].y, vd[0].z, vd[0].w};
+        // the tile's 2 x 2 cells of each channel: the value at its argmax
+        // position (code = 2 dy + dx), zeros elsewhere
+        float* d = dys + ((img * 14 + 2 * ty) * 16 + c0) * WF_DLD + 2 * tx;
 #pragma unroll
-    for (int j = 0; j < PD; ++j) {
-      const int i = tid + j * WF_NT;
-      if (i < ND) {
-        const int pix = i >> 2, img = pix / 196, pp = pix - 196 * img, row = pp / 14;
-        const int col = pp - 14 * row, c0 = 4 * (i & 3);
-        float* d = dys + ((img * 14 + row) * 16 + c0) * WF_DLD + col;
-        d[0] = vd[j].x;
-        d[WF_DLD] = vd[j].y;
-        d[2 * WF_DLD] = vd[j].z;
-        d[3 * WF_DLD] = vd[j].w;
+        for (int c = 0; c < 4; ++c) {
+          const uint32_t code = (vk >> (8 * c)) & 3u;
+#pragma unroll
+          for (int dy = 0; dy < 2; ++dy) {
+            const float v = (code >> 1) == (uint32_t)dy ? vq[c] : 0.f;
+            *reinterpret_cast<float2*>(d + (dy * 16 + c) * WF_DLD) =
+                (code & 1u) ? make_float2(0.f, v) : make_float2(v, 0.f);
+          }
+        }
+      }
+    } else {
+#pragma unroll
+      for (int j = 0; j < PD; ++j) {
+        const int i = tid + j * WF_NT;
+        if (i < ND) {
+          const int pix = i >> 2, img = pix / 196, pp = pix - 196 * img, row = pp / 14;
+          const int col = pp - 14 * row, c0 = 4 * (i & 3);
+          float* d = dys + ((img * 14 + row) * 16 + c0) * WF_DLD + col;
+          d[0] = vd[j].x;
+          d[WF_DLD] = vd[j].y;
+          d[2 * WF_DLD] = vd[j].z;
+          d[3 * WF_DLD] = vd[j].w;
+        }
       }
     }
   }
@@ -1884,13 +1992,14 @@ __device__ __forceinline__ void bwd_filter_wino_block(
   }
 }
 
-template <bool PROF>
+template <bool PROF, bool COMPACT = false>
 __global__ __launch_bounds__(WF_NT) void conv2_bwd_filter_wino_kernel(
     int batch, const float* __restrict__ a1p, const float* __restrict__ dy2,
-    float* __restrict__ part2, float* __restrict__ part_db2, int nwg, const C1Filter c1,
-    unsigned long long* __restrict__ prof) {
+    const uint8_t* __restrict__ idx2, float* __restrict__ part2, float* __restrict__ part_db2,
+    int nwg, const C1Filter c1, unsigned long long* __restrict__ prof) {
   __shared__ float smem[WF_SMEM_ALL];
-  bwd_filter_wino_block<PROF>(blockIdx.x, batch, a1p, dy2, part2, part_db2, nwg, c1, prof, smem);
+  bwd_filter_wino_block<PROF, COMPACT>(blockIdx.x, batch, a1p, dy2, idx2, part2, part_db2, nwg, c1,
+                                       prof, smem);
 }
 
 // Both Winograd conv2 backward products in ONE launch (they depend only on
@@ -2037,12 +2146,15 @@ __device__ void xgmi_fc_gather(const XgmiStepArgs& a, int gb, int ng) {
   xgmi::link_floor(s, t0, a.seg4 * 16);
 }
 
+// COMPACT: dy2 is the compact dp2 with its codes idx2 (both roles); a1 /
+// da1m may be null (bwd_data_wino_block)
+template <bool COMPACT>
 __global__ __launch_bounds__(WF_NT) void conv2_bwd_wino_kernel(
     int nd, const float* __restrict__ Ud,
     const float* __restrict__ a1, int batch, float* __restrict__ da1m,
     const C1Filter c1, const float* __restrict__ a1p, const float* __restrict__ dy2,
-    float* __restrict__ part2, float* __restrict__ part_db2, int nwg, const XgmiStepArgs xfc,
-    unsigned long long* __restrict__ prof) {
+    const uint8_t* __restrict__ idx2, float* __restrict__ part2, float* __restrict__ part_db2,
+    int nwg, const XgmiStepArgs xfc, unsigned long long* __restrict__ prof) {
   // one LDS pool for either role
   __shared__ float smem[WD_SMEM > WF_SMEM_ALL ? WD_SMEM : WF_SMEM_ALL];
   // prof (labs): per block [start, end] of the constant 100 MHz clock
@@ -2066,10 +2178,11 @@ __global__ __launch_bounds__(WF_NT) void conv2_bwd_wino_kernel(
   const int b = (int)blockIdx.x - xfc.nfc;
   if (b < nd) {
     if (threadIdx.x >= WNT) return;
-    bwd_data_wino_block<false, false>(b, nd, dy2, Ud, a1, batch, da1m, FcSgd{}, c1, nullptr, smem);
+    bwd_data_wino_block<false, false, COMPACT>(b, nd, dy2, idx2, Ud, a1, a1p, batch, da1m, FcSgd{},
+                                               c1, nullptr, smem);
   } else {
-    bwd_filter_wino_block<false>(b - nd, batch, a1p, dy2, part2, part_db2, nwg, C1Filter{},
-                                 nullptr, smem);
+    bwd_filter_wino_block<false, COMPACT>(b - nd, batch, a1p, dy2, idx2, part2, part_db2, nwg,
+                                          C1Filter{}, nullptr, smem);
   }
 }
 
@@ -2437,7 +2550,8 @@ void launch_conv2_wino_weights(const float* w2, float* U, float* Ud, hipStream_t
 void launch_conv12_fwd_wino(const C12In& c1, int batch, const float* w2, const float* U,
                             const float* b2, float* a2, uint8_t* idx2, float* w2t, hipStream_t s,
                             unsigned long long* prof, float* a2t) {
-  if (!c1.data || !c1.w1 || !c1.b1 || !c1.a1 || !c1.a1pf || !c1.idx1 || !U)
+  // c1.a1 may be null: the owned rows then go to a1pf alone
+  if (!c1.data || !c1.w1 || !c1.b1 || !c1.a1pf || !c1.idx1 || !U)
     throw std::runtime_error("conv12_fwd_wino: missing operand");
   if (prof)
     conv2_fwd_wino_kernel<true, true><<<batch * 4, WNT, 0, s>>>(nullptr, batch, w2, U, b2, a2, idx2,
@@ -2508,13 +2622,14 @@ void launch_fc_head_eval(const float* h, const float* w4, const float* b4, const
 void launch_fc1_bwd(const float* a2, const uint8_t* idx2, const float* dh, const float* hd,
                     const float* dlog, const float* w1, int batch, float* g_w3, float* g_b3,
                     float* g_w4, float* g_b4, float* dy2, float* dy2t, hipStream_t s,
-                    int roles) {
+                    int roles, float* dp2) {
   if (batch <= 0 || batch % 32 != 0) throw std::runtime_error("fc1_bwd: batch % 32 != 0");
+  if ((roles & 1) && !dy2 && !dp2) throw std::runtime_error("fc1_bwd: neither dy2 nor dp2");
   if (roles <= 0 || roles > 7) throw std::runtime_error("fc1_bwd: roles must be a mask in 1..7");
   const int grid = ((roles & 1) ? (batch / 32) * (FC1_IN / 32) : 0) +
                    ((roles & 2) ? FC1BWD_DW_BLOCKS : 0) + ((roles & 4) ? SMALL_BLOCKS : 0);
   fc1_bwd_kernel<<<grid, 256, 0, s>>>(a2, idx2, dh, hd, dlog, w1, batch, g_w3, g_b3, g_w4, g_b4,
-                                      dy2, dy2t, roles);
+                                      dy2, dy2t, dp2, roles);
 }
 
 void launch_fc1_bwd_weights(const float* a2, const float* dh, const float* hd, const float* dlog,
@@ -2573,19 +2688,43 @@ void launch_conv2_bwd_data_l2(const float* dy2t, const float* w2t, const float* 
                                                                      sg);
 }
 
+// the dY2 operand of the Winograd backward launchers: dense dy2, or
+// (dy2 == nullptr) the compact dp2 + idx2
+static const float* dy2_operand(const char* who, const float* dy2, const float* dp2,
+                                const uint8_t* idx2) {
+  if (dy2 != nullptr) return dy2;
+  if (dp2 == nullptr || idx2 == nullptr)
+    throw std::runtime_error(std::string(who) + ": neither dy2 nor dp2 + idx2");
+  return dp2;
+}
+
 void launch_conv2_bwd_data_wino(const float* dy2, const float* Ud, const float* a1, int batch,
                                 float* da1m, hipStream_t s, const FcSgdArgs* fc_sgd,
-                                const C1FilterArgs* c1, unsigned long long* prof) {
+                                const C1FilterArgs* c1, unsigned long long* prof,
+                                const float* dp2, const uint8_t* idx2, const float* a1pf) {
+  const float* dy = dy2_operand("conv2_bwd_data_wino", dy2, dp2, idx2);
+  if (!a1 && !a1pf) throw std::runtime_error("conv2_bwd_data_wino: neither a1 nor a1pf");
+  if (!da1m && !(c1 && c1->part1))
+    throw std::runtime_error("conv2_bwd_data_wino: no da1m and no conv1 filter gradient");
   FcSgd sg = fc_sgd_args(fc_sgd);
   if (sg.w1b) throw std::runtime_error("conv2_bwd_data_wino: the fp32 FC SGD has no shadows");
   // the FC SGD runs in 256-thread units, two per (conv) block
   sg.nblk = 2 * batch * 4;
-  if (prof)
-    conv2_bwd_data_wino_kernel<true><<<batch * 4, WNT, 0, s>>>(dy2, Ud, a1, batch, da1m, sg,
-                                                              c1_args(c1), prof);
-  else
-    conv2_bwd_data_wino_kernel<false><<<batch * 4, WNT, 0, s>>>(dy2, Ud, a1, batch, da1m, sg,
-                                                               c1_args(c1));
+#define BWD_DATA(PROF_, COMPACT_)                                                    \
+  conv2_bwd_data_wino_kernel<PROF_, COMPACT_><<<batch * 4, WNT, 0, s>>>(            \
+      dy, idx2, Ud, a1, a1pf, batch, da1m, sg, c1_args(c1), prof)
+  if (dy2 == nullptr) {
+    if (prof)
+      BWD_DATA(true, true);
+    else
+      BWD_DATA(false, true);
+  } else {
+    if (prof)
+      BWD_DATA(true, false);
+    else
+      BWD_DATA(false, false);
+  }
+#undef BWD_DATA
 }
 
 void launch_conv2_bwd_filter(const float* a1p, const float* dy2, int batch, float* part2,
@@ -2610,12 +2749,18 @@ size_t part2_floats_wino(int batch) {
 }
 
 void launch_conv2_bwd_filter_wino(const float* a1p, const float* dy2, int batch, float* part2,
-                                  hipStream_t s, const C1FilterArgs* c1) {
+                                  hipStream_t s, const C1FilterArgs* c1, const float* dp2,
+                                  const uint8_t* idx2) {
+  const float* dy = dy2_operand("conv2_bwd_filter_wino", dy2, dp2, idx2);
   const int G = conv2_wino_filter_groups(batch);
   const C1Filter c = c1_args(c1);
   const int n1 = c.part1 ? conv1_filter_blocks(batch, 1) : 0;
-  conv2_bwd_filter_wino_kernel<false><<<8 * G + n1, WF_NT, 0, s>>>(
-      batch, a1p, dy2, part2, part2 + (size_t)G * 51200, 8 * G, c, nullptr);
+  if (dy2 == nullptr)
+    conv2_bwd_filter_wino_kernel<false, true><<<8 * G + n1, WF_NT, 0, s>>>(
+        batch, a1p, dy, idx2, part2, part2 + (size_t)G * 51200, 8 * G, c, nullptr);
+  else
+    conv2_bwd_filter_wino_kernel<false, false><<<8 * G + n1, WF_NT, 0, s>>>(
+        batch, a1p, dy, idx2, part2, part2 + (size_t)G * 51200, 8 * G, c, nullptr);
 }
 
 // labs: per-block clock stamps of the merged conv2 backward (null: off)
@@ -2623,7 +2768,11 @@ static unsigned long long* g_c2bw_prof = nullptr;
 
 void launch_conv2_bwd_wino(const float* Ud, const float* a1, const float* a1p, const float* dy2,
                            int batch, float* da1m, float* part2, hipStream_t s,
-                           const C1FilterArgs* c1, const XgmiStepArgs* xfc) {
+                           const C1FilterArgs* c1, const XgmiStepArgs* xfc, const float* dp2,
+                           const uint8_t* idx2) {
+  const float* dy = dy2_operand("conv2_bwd_wino", dy2, dp2, idx2);
+  if (!da1m && !(c1 && c1->part1))
+    throw std::runtime_error("conv2_bwd_wino: no da1m and no conv1 filter gradient");
   const int nd = batch * 4;
   const int G = conv2_wino_filter_groups(batch);
   XgmiStepArgs xa{};
@@ -2631,18 +2780,29 @@ void launch_conv2_bwd_wino(const float* Ud, const float* a1, const float* a1p, c
     xa = *xfc;
     xgmi_fc_plan(xa, WF_NT, XS_FC_ROLE_BLOCKS);
   }
-  conv2_bwd_wino_kernel<<<xa.nfc + nd + 8 * G, WF_NT, 0, s>>>(
-      nd, Ud, a1, batch, da1m, c1_args(c1), a1p, dy2, part2, part2 + (size_t)G * 51200, 8 * G, xa,
-      g_c2bw_prof);
+  if (dy2 == nullptr)
+    conv2_bwd_wino_kernel<true><<<xa.nfc + nd + 8 * G, WF_NT, 0, s>>>(
+        nd, Ud, a1, batch, da1m, c1_args(c1), a1p, dy, idx2, part2, part2 + (size_t)G * 51200,
+        8 * G, xa, g_c2bw_prof);
+  else
+    conv2_bwd_wino_kernel<false><<<xa.nfc + nd + 8 * G, WF_NT, 0, s>>>(
+        nd, Ud, a1, batch, da1m, c1_args(c1), a1p, dy, idx2, part2, part2 + (size_t)G * 51200,
+        8 * G, xa, g_c2bw_prof);
 }
 
 void set_conv2_bwd_wino_prof(unsigned long long* p) { g_c2bw_prof = p; }
 
 void launch_conv2_bwd_filter_wino_prof(const float* a1p, const float* dy2, int batch,
-                                       float* part2, unsigned long long* prof, hipStream_t s) {
+                                       float* part2, unsigned long long* prof, hipStream_t s,
+                                       const float* dp2, const uint8_t* idx2) {
+  const float* dy = dy2_operand("conv2_bwd_filter_wino_prof", dy2, dp2, idx2);
   const int G = conv2_wino_filter_groups(batch);
-  conv2_bwd_filter_wino_kernel<true><<<8 * G, WF_NT, 0, s>>>(
-      batch, a1p, dy2, part2, part2 + (size_t)G * 51200, 8 * G, C1Filter{}, prof);
+  if (dy2 == nullptr)
+    conv2_bwd_filter_wino_kernel<true, true><<<8 * G, WF_NT, 0, s>>>(
+        batch, a1p, dy, idx2, part2, part2 + (size_t)G * 51200, 8 * G, C1Filter{}, prof);
+  else
+    conv2_bwd_filter_wino_kernel<true, false><<<8 * G, WF_NT, 0, s>>>(
+        batch, a1p, dy, idx2, part2, part2 + (size_t)G * 51200, 8 * G, C1Filter{}, prof);
 }
 
 C1Filter c1_args(const C1FilterArgs* a) {
@@ -3254,7 +3414,7 @@ __global__ __launch_bounds__(256) void xgmi_fac_gather_kernel(const XgmiFacArgs 
 __global__ __launch_bounds__(256) void fc1_bwd_dx_fac_kernel(
     const float* __restrict__ a2, const uint8_t* __restrict__ idx2, const float* __restrict__ dh,
     const float* __restrict__ w1, int batch, float* __restrict__ dy2, float* __restrict__ dy2t,
-    int ngb, const XgmiFacArgs f) {
+    float* __restrict__ dp2, int ngb, const XgmiFacArgs f) {
   __shared__ float smem[4 * FC1DX_WAVE];
   if ((int)blockIdx.x < ngb) {
     xgmi_fac_gather_block(f, blockIdx.x, ngb, reinterpret_cast<unsigned*>(smem));
@@ -3262,7 +3422,7 @@ __global__ __launch_bounds__(256) void fc1_bwd_dx_fac_kernel(
   }
   const int nb = (int)gridDim.x - ngb;
   const int L = xcd_remap((int)blockIdx.x - ngb, nb);
-  fc1_bwd_dx(L, a2, idx2, dh, w1, batch, dy2, dy2t, smem);
+  fc1_bwd_dx(L, a2, idx2, dh, w1, batch, dy2, dy2t, dp2, smem);
 }
 
 static void check_fac(const XgmiFacArgs& a) {
@@ -3277,13 +3437,15 @@ static void check_fac(const XgmiFacArgs& a) {
 
 void launch_fc1_bwd_dx_fac_gather(const float* a2, const uint8_t* idx2, const float* dh,
                                   const float* w1, int batch, float* dy2, float* dy2t,
-                                  const XgmiFacArgs& f, hipStream_t s) {
+                                  const XgmiFacArgs& f, hipStream_t s, float* dp2) {
   if (batch <= 0 || batch % 32 != 0) throw std::runtime_error("fc1_bwd: batch % 32 != 0");
+  if (!dy2 && !dp2) throw std::runtime_error("fc1_bwd: neither dy2 nor dp2");
   check_fac(f);
   // 196 dX blocks at B = 64 + 56 gather blocks: one round on 256 CUs
   const int ndx = (batch / 32) * (FC1_IN / 32);
   const int ngb = f.sync.lean ? 16 : std::max(16, std::min(128, 256 - ndx));
-  fc1_bwd_dx_fac_kernel<<<ngb + ndx, 256, 0, s>>>(a2, idx2, dh, w1, batch, dy2, dy2t, ngb, f);
+  fc1_bwd_dx_fac_kernel<<<ngb + ndx, 256, 0, s>>>(a2, idx2, dh, w1, batch, dy2, dy2t, dp2,
+                                                  ngb, f);
 }
 
 __global__ __launch_bounds__(256) void fc1_small_grads_kernel(const float* __restrict__ dh,

@@ -65,7 +65,9 @@ void MnistExecutor::enqueue_fwd_bwd(hipStream_t s, bool finalize,
   cf.n_local = p.n_local;
   cf.w1 = W + p.off_w1;
   cf.b1 = W + p.off_b1;
-  cf.a1 = P<float>(p.a1);
+  // compact Winograd backward (MnistPtrs::dp2): no a1 / dy2 / da1m buffers
+  const bool compact = p.wino && p.dp2 != 0;
+  cf.a1 = compact ? nullptr : P<float>(p.a1);
   cf.a1pf = P<float>(p.a1pf);
   cf.idx1 = P<uint8_t>(p.idx1);
   if (p.wino) {
@@ -97,21 +99,39 @@ void MnistExecutor::enqueue_fwd_bwd(hipStream_t s, bool finalize,
   // (SCHED_XGMI_FAC: dX | the peers' factor rows over the links)
   if (xfac)
     mnist::launch_fc1_bwd_dx_fac_gather(P<const float>(p.a2), P<const uint8_t>(p.idx2),
-                                        P<const float>(p.dh), W + p.off_w3, B, P<float>(p.dy2),
-                                        p.wino ? nullptr : P<float>(p.dy2t), *xfac, s);
+                                        P<const float>(p.dh), W + p.off_w3, B,
+                                        compact ? nullptr : P<float>(p.dy2),
+                                        p.wino ? nullptr : P<float>(p.dy2t), *xfac, s,
+                                        compact ? P<float>(p.dp2) : nullptr);
   else
     mnist::launch_fc1_bwd(P<const float>(p.a2), P<const uint8_t>(p.idx2), P<const float>(p.dh),
                           P<const float>(p.hd), P<const float>(p.dlog), W + p.off_w3, B,
                           G + p.off_w3, G + p.off_b3, G + p.off_w4, G + p.off_b4,
-                          P<float>(p.dy2), p.wino ? nullptr : P<float>(p.dy2t), s,
-                          factors ? 1 : (fc1_dw_fused ? 5 : 7));
+                          compact ? nullptr : P<float>(p.dy2),
+                          p.wino ? nullptr : P<float>(p.dy2t), s,
+                          factors ? 1 : (fc1_dw_fused ? 5 : 7),
+                          compact ? P<float>(p.dp2) : nullptr);
   HIP_CHECK(hipEventRecord(ev_dw_, s));
   // conv1 filter grad: Winograd - in the bwd-data blocks' epilogue, from the
   // dA1 values they produce; direct - role blocks of the filter-grad launch
   const mnist::C1FilterArgs c1{P<const float>(p.train_x), step, p.n_local,
                                P<const float>(p.da1m), P<const uint8_t>(p.idx1),
                                P<float>(p.part1)};
-  if (p.wino && fc_sgd == nullptr) {  // bwd-data (+ conv1 filter grad) and filter grad: one launch
+  if (compact) {
+    // dp2 + idx2 instead of dy2, the ReLU1 mask from a1pf, no dA1 store (the
+    // conv1 filter gradient is formed in the bwd-data blocks: c1.part1)
+    const float* dp2 = P<const float>(p.dp2);
+    const uint8_t* idx2 = P<const uint8_t>(p.idx2);
+    if (fc_sgd == nullptr) {
+      mnist::launch_conv2_bwd_wino(P<const float>(p.wino_ud), nullptr, P<const float>(p.a1pf),
+                                   nullptr, B, nullptr, P<float>(p.part2), s, &c1, xfc, dp2, idx2);
+    } else {
+      mnist::launch_conv2_bwd_data_wino(nullptr, P<const float>(p.wino_ud), nullptr, B, nullptr, s,
+                                        fc_sgd, &c1, nullptr, dp2, idx2, P<const float>(p.a1pf));
+      mnist::launch_conv2_bwd_filter_wino(P<const float>(p.a1pf), nullptr, B, P<float>(p.part2),
+                                          s, nullptr, dp2, idx2);
+    }
+  } else if (p.wino && fc_sgd == nullptr) {  // bwd-data (+ conv1 filter grad) and filter grad: one launch
     mnist::launch_conv2_bwd_wino(P<const float>(p.wino_ud), P<const float>(p.a1),
                                  P<const float>(p.a1pf), P<const float>(p.dy2), B,
                                  P<float>(p.da1m), P<float>(p.part2), s, &c1, xfc);

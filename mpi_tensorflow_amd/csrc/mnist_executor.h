@@ -72,6 +72,11 @@ struct MnistPtrs {
   // fp32 Winograd step (optional): a2 also feature-major [3136][batch], written
   // by the conv2 forward for the LDS-free fc1 forward (0: the LDS-staged one)
   uintptr_t a2ft = 0;
+  // fp32 Winograd step, compact backward (dp2 != 0): fc1 backward writes the
+  // pooled gradient dp2 [batch][7][7][64] (codes: idx2) instead of the dense
+  // dy2, the forward stores a1 only as a1pf and the bwd-data blocks do not
+  // store dA1 - a1 / dy2 / da1m above are then unused and may be 0
+  uintptr_t dp2 = 0;
 };
 
 namespace mnist {

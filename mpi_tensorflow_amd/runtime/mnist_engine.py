@@ -183,8 +183,15 @@ class NativeMnistEngine(MnistEngineBase):
 
     def __init__(self, cfg, train_x, train_y, device, rank=0, world=1, comm=None,
                  force_sync: bool = False, fc1_feature_major: bool = False,
-                 xcomm: Optional[XgmiDeviceComm] = None):
-        """fc1_feature_major (labs): the fp32 Winograd step's conv2 forward
+                 xcomm: Optional[XgmiDeviceComm] = None, compact_bwd: bool = True):
+        """compact_bwd: the fp32 Winograd step passes dY2 to the conv2 backward
+        as the pooled gradient dp2 [B][7][7][64] + the pool2 argmax codes
+        (idx2) instead of the dense NHWC image (75 % structural zeros), keeps
+        a1 only in its zero-bordered form (a1pf) and does not store the masked
+        dA1, which no kernel of that step reads.  Same results bit for bit;
+        False (labs) restores the dense dY2 and both stores on the same build.
+
+        fc1_feature_major (labs): the fp32 Winograd step's conv2 forward
         also writes a2 feature-major and the fc1 forward reads its operands
         straight from L2 (fc1_fwd_t_kernel) instead of staging them through
         LDS.  Equal in isolation (8.0 vs 8.3 us), but 3 us SLOWER in the step
@@ -233,6 +240,11 @@ class NativeMnistEngine(MnistEngineBase):
                              part2=torch.empty(k.part2_floats_wino(B), **f32))
             if fc1_feature_major:  # a2 feature-major, the fc1 forward's direct operand
                 self.bufs["a2ft"] = torch.empty(M.FC1_IN * B, **f32)
+            if compact_bwd:
+                self.bufs["dp2"] = torch.empty(B * M.FC1_IN, **f32)
+                for name in ("a1", "dy2", "dy2t", "da1m"):  # not used by this step
+                    self.bufs[name] = torch.empty(0, **f32)
+        self.compact_bwd = self.wino and compact_bwd
         self.fac = None
         hcomm = comm.native_handle if (self.grad_sync and comm is not None) else None
         nfac = hcomm.size if hcomm is not None else 1

@@ -22,15 +22,20 @@ def main():
     ap.add_argument("--step-only", action="store_true",
                     help="only the graph-replayed step per FC SGD placement (any dtype)")
     ap.add_argument("--rounds", default="0,2", help="FC SGD placements to time (fc_sgd_rounds)")
+    ap.add_argument("--dense-bwd", action="store_true",
+                    help="--step-only: the fp32 Winograd step with the dense dY2 and the a1 / da1m "
+                         "stores (compact_bwd=False) instead of the compact backward")
     a = ap.parse_args()
     dev = torch.device("cuda:0")
     x, y = synthetic_rows("train", 0, 4096)
     cfg = C.TrainConfig(batch_size=a.batch, graph=False, dtype=a.dtype).validate()
     if a.step_only:
-        e = NativeMnistEngine(cfg, x, y, dev)
+        e = NativeMnistEngine(cfg, x, y, dev, compact_bwd=not a.dense_bwd)
+        print(f"compact_bwd={e.compact_bwd}")
         step_placements(e, [int(r) for r in a.rounds.split(",")])
         return
-    e = NativeMnistEngine(cfg, x, y, dev, fc1_feature_major=True)  # + the a2ft lab buffer
+    # + the a2ft lab buffer; the dense backward buffers (a1, dy2, da1m) feed the isolated launches
+    e = NativeMnistEngine(cfg, x, y, dev, fc1_feature_major=True, compact_bwd=False)
     e.train(5)
     e.forward_backward_only()
     torch.cuda.synchronize()

@@ -25,7 +25,9 @@ def main():
     dev = torch.device("cuda:0")
     x, y = synthetic_rows("train", 0, 4096)
     cfg = C.TrainConfig(graph=False).validate()
-    e = NativeMnistEngine(cfg, x, y, dev)
+    # the dense backward buffers (a1, dy2, da1m) feed the isolated launches;
+    # the compact forms (dp2 + idx2, mask from a1pf, no dA1 store) are timed next to them
+    e = NativeMnistEngine(cfg, x, y, dev, compact_bwd=False)
     e.train(3)
     e.forward_backward_only()
     torch.cuda.synchronize()
@@ -35,7 +37,29 @@ def main():
     s = stream_handle()
     k.conv2_wino_weights(W("conv2_weight"), ptr(b["wino_u"]), ptr(b["wino_ud"]), s)
     w2t = torch.empty(25 * 64 * 32, device=dev)
+    dp2 = torch.empty(B * 7 * 7 * 64, device=dev)
+    k.fc1_bwd_dp2(ptr(b["a2"]), ptr(b["idx2"]), ptr(b["dh"]), ptr(b["hd"]), ptr(b["dlog"]),
+                  W("fc1_weight"), B, 0, 0, 0, 0, ptr(dp2), s, 1)
+    part1 = torch.zeros(B * 4 * 832, device=dev)
+    c1 = (ptr(e.train_x), ptr(e.step_dev), e.n_local, ptr(b["idx1"]), ptr(part1), s)
+    G3 = lambda n: ptr(e.grads) + 4 * lay.offsets[n]  # noqa: E731
+    fcg = (G3("fc1_weight"), G3("fc1_bias"), G3("fc2_weight"), G3("fc2_bias"))
+    fca = (ptr(b["a2"]), ptr(b["idx2"]), ptr(b["dh"]), ptr(b["hd"]), ptr(b["dlog"]), W("fc1_weight"), B)
     ops = {
+        "fc1_bwd(dense dy2)": lambda: k.fc1_bwd(*fca, *fcg, ptr(b["dy2"]), 0, s),
+        "fc1_bwd(dp2)": lambda: k.fc1_bwd_dp2(*fca, *fcg, ptr(dp2), s),
+        "wgrad(wino, dp2)": lambda: k.conv2_bwd_filter_wino_dp2(ptr(b["a1pf"]), ptr(dp2), ptr(b["idx2"]),
+                                                              B, ptr(b["part2"]), s),
+        "bwd_data(wino)+c1": lambda: k.conv2_bwd_data_wino_c1(
+            ptr(b["dy2"]), 0, 0, ptr(b["wino_ud"]), ptr(b["a1"]), ptr(b["a1pf"]), B, ptr(b["da1m"]), *c1),
+        "bwd_data(wino, dp2)+c1": lambda: k.conv2_bwd_data_wino_c1(
+            0, ptr(dp2), ptr(b["idx2"]), ptr(b["wino_ud"]), 0, ptr(b["a1pf"]), B, 0, *c1),
+        "conv2_bwd(wino, merged)": lambda: k.conv2_bwd_wino(
+            ptr(b["wino_ud"]), ptr(b["a1"]), ptr(b["a1pf"]), ptr(b["dy2"]), 0, 0, B, ptr(b["da1m"]),
+            ptr(b["part2"]), *c1),
+        "conv2_bwd(wino, merged, dp2)": lambda: k.conv2_bwd_wino(
+            ptr(b["wino_ud"]), 0, ptr(b["a1pf"]), 0, ptr(dp2), ptr(b["idx2"]), B, 0, ptr(b["part2"]),
+            *c1),
         "conv2_fwd(direct)": lambda: k.conv2_fwd(ptr(b["a1"]), B, W("conv2_weight"), W("conv2_bias"),
                                                  ptr(b["a2"]), ptr(b["idx2"]), ptr(w2t), s),
         "conv2_fwd(wino)": lambda: k.conv2_fwd_wino(ptr(b["a1"]), B, W("conv2_weight"), ptr(b["wino_u"]),
@@ -52,25 +76,31 @@ def main():
     if a.phases:
         G = k.conv2_wino_filter_groups(B)
         nw = 12
-        prof = torch.zeros(8 * G * nw * 5, dtype=torch.int64, device=dev)
-        for _ in range(5):
-            k.conv2_bwd_filter_wino_prof(ptr(b["a1pf"]), ptr(b["dy2"]), B, ptr(b["part2"]), ptr(prof), s)
-        torch.cuda.synchronize()
-        t = prof.view(8 * G, nw, 5).double()
-        t0 = t[..., 0].min()
-        d = t[..., 1:] - t[..., :-1]
-        names = ["staging", "main loop", "db + S_a", "dW + stores"]
-        print("wgrad(wino) phases, cycles per wave: mean / max")
-        for i, nm in enumerate(names):
-            print(f"  {nm:12s} {d[..., i].mean().item():9.0f} {d[..., i].max().item():9.0f}")
-        print(f"  span (first start -> last end) {(t[..., 4].max() - t0).item():.0f} cycles; "
-              f"block start spread {(t[..., 0].max() - t0).item():.0f}")
+        for form in ("dense", "dp2"):
+            prof = torch.zeros(8 * G * nw * 5, dtype=torch.int64, device=dev)
+            for _ in range(5):
+                if form == "dense":
+                    k.conv2_bwd_filter_wino_prof(ptr(b["a1pf"]), ptr(b["dy2"]), B, ptr(b["part2"]),
+                                                 ptr(prof), s)
+                else:
+                    k.conv2_bwd_filter_wino_dp2(ptr(b["a1pf"]), ptr(dp2), ptr(b["idx2"]), B,
+                                                ptr(b["part2"]), s, ptr(prof))
+            torch.cuda.synchronize()
+            t = prof.view(8 * G, nw, 5).double()
+            t0 = t[..., 0].min()
+            d = t[..., 1:] - t[..., :-1]
+            names = ["staging", "main loop", "db + S_a", "dW + stores"]
+            print(f"wgrad(wino, {form}) phases, cycles per wave: mean / max")
+            for i, nm in enumerate(names):
+                print(f"  {nm:12s} {d[..., i].mean().item():9.0f} {d[..., i].max().item():9.0f}")
+            print(f"  span (first start -> last end) {(t[..., 4].max() - t0).item():.0f} cycles; "
+                  f"block start spread {(t[..., 0].max() - t0).item():.0f}")
     if a.phases:
         nb, nw = B * 4, 8
         W_ = lambda n: ptr(e.params) + 4 * lay.offsets[n]  # noqa: E731
         pf = torch.zeros(nb * nw * 5, dtype=torch.int64, device=dev)
         pb = torch.zeros(nb * nw * 7, dtype=torch.int64, device=dev)
-        part1 = torch.zeros(B * 4 * 832, device=dev)
+        pc = torch.zeros(nb * nw * 7, dtype=torch.int64, device=dev)
         for _ in range(5):
             k.conv12_fwd_wino(ptr(e.train_x), ptr(e.step_dev), e.n_local, B, W_("conv1_weight"),
                               W_("conv1_bias"), ptr(b["a1"]), ptr(b["a1pf"]), ptr(b["idx1"]),
@@ -79,10 +109,16 @@ def main():
             k.conv2_bwd_data_wino_prof(ptr(b["dy2"]), ptr(b["wino_ud"]), ptr(b["a1"]), B,
                                        ptr(b["da1m"]), ptr(e.train_x), ptr(e.step_dev), e.n_local,
                                        ptr(b["idx1"]), ptr(part1), ptr(pb), s)
+            k.conv2_bwd_data_wino_c1(0, ptr(dp2), ptr(b["idx2"]), ptr(b["wino_ud"]), 0,
+                                     ptr(b["a1pf"]), B, 0, *c1, ptr(pc))
         torch.cuda.synchronize()
         for nm, t, names in (("conv12_fwd(wino)", pf.view(nb, nw, 5).double(),
                               ["conv1 -> halo", "input transform", "products", "sums + epilogue"]),
                              ("bwd_data(wino)+c1", pb.view(nb, nw, 7).double(),
+                              ["h0 transform", "h0 products", "h1 transform", "h1 products",
+                               "sums + dA1", "conv1 wgrad"]),
+                             ("bwd_data(wino, dp2, a1pf mask, no dA1 store)+c1",
+                              pc.view(nb, nw, 7).double(),
                               ["h0 transform", "h0 products", "h1 transform", "h1 products",
                                "sums + dA1", "conv1 wgrad"])):
             t0 = t[..., 0].min()
