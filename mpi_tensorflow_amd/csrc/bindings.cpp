@@ -365,6 +365,34 @@ PYBIND11_MODULE(_C, m) {
     check_launch();
   });
 
+  // The conv part of the step's SGD launch on its own (tests): grads summed
+  // from the slabs part2 / part1, or with part2 == 0 read from the flat g;
+  // U / Ud (both or neither): the updated conv2 filters' Winograd transforms.
+  k.def("sgd_step_conv", [](uintptr_t w, uintptr_t g, uintptr_t mom, int off_w2, int off_b2,
+                            int off_w1, int off_b1, float momentum, float gscale, uintptr_t lr,
+                            uintptr_t part2, int ngroups, uintptr_t part1, int nblk1, uintptr_t U,
+                            uintptr_t Ud, uintptr_t s) {
+    mnist::SgdStepArgs a;
+    a.w = P<float>(w);
+    a.g = P<const float>(g);
+    a.mom = P<float>(mom);
+    a.momentum = momentum;
+    a.gscale = gscale;
+    a.lr = P<const float>(lr);
+    a.off_w2 = off_w2;
+    a.off_b2 = off_b2;
+    a.off_w1 = off_w1;
+    a.off_b1 = off_b1;
+    a.part2 = P<const float>(part2);
+    a.ngroups = ngroups;
+    a.part1 = P<const float>(part1);
+    a.nblk1 = nblk1;
+    a.wino_u = P<float>(U);
+    a.wino_ud = P<float>(Ud);
+    mnist::launch_sgd_step(a, S(s));
+    check_launch();
+  });
+
   auto o = m.def_submodule("optim", "flat-buffer optimizer kernels");
   o.def("sgd_momentum", [](uintptr_t w, uintptr_t g, uintptr_t mom, long long n, long long l2_end,
                            float l2, float momentum, float gscale, uintptr_t lr_ptr,

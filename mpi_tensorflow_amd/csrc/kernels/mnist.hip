@@ -2867,11 +2867,32 @@ __device__ __forceinline__ void sgd_elem(float* w, float* m, float g, float lr, 
   *w -= lr * mv;
 }
 
+// sgd_elem on a parameter and momentum already in registers (same expressions)
+__device__ __forceinline__ void sgd_elem_v(float& w, float& m, float g, float lr, float mu) {
+  const float mv = mu * m + g;
+  m = mv;
+  w -= lr * mv;
+}
+
 // dW2 float4 i (HWIO order): slab sum in group order (slab_sum4), or
 // the all-reduced flat gradient
 __device__ __forceinline__ float4 conv2_grad4(const SgdFinArgs& a, int i) {
   if (a.flat) return reinterpret_cast<const float4*>(a.g + a.off_w2)[i];
   return slab_sum4(reinterpret_cast<const float4*>(a.part2) + i, a.ngroups);
+}
+
+// Rows A0 .. A0 + 2 of the Winograd transform of the 16 filters in wl [tap][co]
+// (UD: the flipped filters, Ud layout) for channel ci, co = co0 + lane cl
+template <int A0, bool UD>
+__device__ __forceinline__ void sgd_wino_rows(const float* wl, float* dst, int ci, int co0,
+                                              int cl) {
+  float g[25], u[36];
+#pragma unroll
+  for (int t = 0; t < 25; ++t) g[t] = wl[(UD ? 24 - t : t) * 16 + cl];
+  wino::filter_tile_rows<A0, A0 + 3>(g, u);
+#pragma unroll
+  for (int p = 6 * A0; p < 6 * A0 + 18; ++p)
+    dst[UD ? wino_ud_index(p, ci, co0 + cl) : wino_u_index(p, ci, co0 + cl)] = u[p];
 }
 
 // conv2 weights of one input channel ci and 16 output channels (block b: ci
@@ -2895,22 +2916,17 @@ __device__ void sgd_conv2_wino(const SgdFinArgs& a, int blk, float lr) {
     *reinterpret_cast<float4*>(wl + t * 16 + 4 * c4) = wv;
   }
   __syncthreads();
-  if (tid < 32) {
-    const int cl = tid & 15, co = cq * 16 + cl;
-    float g[25], u[36];
-    if (tid < 16) {
-#pragma unroll
-      for (int t = 0; t < 25; ++t) g[t] = wl[t * 16 + cl];
-      wino::filter_tile(g, u);
-#pragma unroll
-      for (int p = 0; p < 36; ++p) a.U[wino_u_index(p, ci, co)] = u[p];
-    } else {
-#pragma unroll
-      for (int t = 0; t < 25; ++t) g[t] = wl[(24 - t) * 16 + cl];
-      wino::filter_tile(g, u);
-#pragma unroll
-      for (int p = 0; p < 36; ++p) a.Ud[wino_ud_index(p, ci, co)] = u[p];
-    }
+  // the two transforms over the four waves: wave = (U / Ud, point rows 0 .. 2
+  // / 3 .. 5), lanes 0 .. 15 = co.  The split is uniform per wave, so the
+  // coefficients stay immediates (a per-thread point index made them table
+  // loads; one wave of 16 + 16 threads ran 25 -> 36 with 36 stores a thread)
+  const int cl = tid & 63;
+  if (cl >= 16) return;
+  switch (tid >> 6) {
+    case 0: sgd_wino_rows<0, false>(wl, a.U, ci, cq * 16, cl); break;
+    case 1: sgd_wino_rows<3, false>(wl, a.U, ci, cq * 16, cl); break;
+    case 2: sgd_wino_rows<0, true>(wl, a.Ud, ci, cq * 16, cl); break;
+    default: sgd_wino_rows<3, true>(wl, a.Ud, ci, cq * 16, cl); break;
   }
 }
 
@@ -2985,8 +3001,14 @@ __device__ __forceinline__ void sgd_finalize_body(const SgdFinArgs& a, float* ti
   const int lane = tid & 63;
   // (gscale: the conv bias / conv1 grads go through the sgd4 form
   // fma(0, w, g * gs), as in optim::sgd_momentum_flat)
+  // Both roles below request the parameters and momenta they update ahead of
+  // the partial-sum loads (every lane, one address a wave): loaded after the
+  // wave reduction they cost lane 0 dependent round trips, one per sgd_elem
+  // (w and mom may alias, so each call's loads also followed the last stores).
+  // Every parameter has exactly one owning wave.
   if (blk < 16) {  // conv2 bias: one wave per channel
     const int co = blk * 4 + (tid >> 6);
+    float wv = a.w[a.off_b2 + co], mv = a.mom[a.off_b2 + co];
     float s = 0.f;
     if (a.flat) {
       s = a.g[a.off_b2 + co];
@@ -2995,8 +3017,9 @@ __device__ __forceinline__ void sgd_finalize_body(const SgdFinArgs& a, float* ti
       s = wave_sum(s);
     }
     if (lane == 0) {
-      float* w = a.w + a.off_b2 + co;
-      sgd_elem(w, a.mom + a.off_b2 + co, __builtin_fmaf(0.f, *w, s * a.gscale), lr, a.momentum);
+      sgd_elem_v(wv, mv, __builtin_fmaf(0.f, wv, s * a.gscale), lr, a.momentum);
+      a.mom[a.off_b2 + co] = mv;
+      a.w[a.off_b2 + co] = wv;
     }
     return;
   }
@@ -3007,6 +3030,21 @@ __device__ __forceinline__ void sgd_finalize_body(const SgdFinArgs& a, float* ti
   // per parameter did
   const int o0 = (blk * 4 + (tid >> 6)) * 4;
   if (o0 >= 832) return;
+  // o0 and 800 are multiples of 4: the four are all weights or all biases
+  const int off = o0 < 800 ? a.off_w1 + o0 : a.off_b1 + (o0 - 800);
+  float* wp = a.w + off;
+  float* mp = a.mom + off;
+  const bool vec = ((reinterpret_cast<uintptr_t>(wp) | reinterpret_cast<uintptr_t>(mp)) & 15) == 0;
+  float wv[4], mv[4];
+  if (vec) {
+    const float4 w4 = *reinterpret_cast<const float4*>(wp);
+    const float4 m4 = *reinterpret_cast<const float4*>(mp);
+    wv[0] = w4.x, wv[1] = w4.y, wv[2] = w4.z, wv[3] = w4.w;
+    mv[0] = m4.x, mv[1] = m4.y, mv[2] = m4.z, mv[3] = m4.w;
+  } else {
+#pragma unroll
+    for (int k = 0; k < 4; ++k) wv[k] = wp[k], mv[k] = mp[k];
+  }
   float s[4] = {0.f, 0.f, 0.f, 0.f};
   if (a.flat) {
 #pragma unroll
@@ -3028,11 +3066,14 @@ __device__ __forceinline__ void sgd_finalize_body(const SgdFinArgs& a, float* ti
   }
   if (lane == 0) {
 #pragma unroll
-    for (int k = 0; k < 4; ++k) {
-      const int o = o0 + k;
-      const int off = o < 800 ? a.off_w1 + o : a.off_b1 + (o - 800);
-      sgd_elem(a.w + off, a.mom + off, __builtin_fmaf(0.f, a.w[off], s[k] * a.gscale), lr,
-               a.momentum);
+    for (int k = 0; k < 4; ++k)
+      sgd_elem_v(wv[k], mv[k], __builtin_fmaf(0.f, wv[k], s[k] * a.gscale), lr, a.momentum);
+    if (vec) {
+      *reinterpret_cast<float4*>(mp) = make_float4(mv[0], mv[1], mv[2], mv[3]);
+      *reinterpret_cast<float4*>(wp) = make_float4(wv[0], wv[1], wv[2], wv[3]);
+    } else {
+#pragma unroll
+      for (int k = 0; k < 4; ++k) mp[k] = mv[k], wp[k] = wv[k];
     }
   }
 }

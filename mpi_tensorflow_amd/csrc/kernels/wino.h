@@ -48,20 +48,25 @@ __host__ __device__ __forceinline__ void bt6(const float* in, float* out) {
   }
 }
 
-// out[a] = sum_k kG[a][k] in[k*stride]  (filter side, 1-D)
-template <int S_IN, int S_OUT>
-__host__ __device__ __forceinline__ void g6(const float* in, float* out) {
+// out[a] = sum_k kG[a][k] in[k*stride] for a in [A0, A1)  (filter side, 1-D)
+template <int S_IN, int S_OUT, int A0, int A1>
+__host__ __device__ __forceinline__ void g6_rows(const float* in, float* out) {
   // no FMA contraction: the filter transform is computed by several kernels
   // (the per-step transform and the fused SGD) and must round identically
 #pragma clang fp contract(off)
 #pragma unroll
-  for (int a = 0; a < 6; ++a) {
+  for (int a = A0; a < A1; ++a) {
     float s = 0.f;
 #pragma unroll
     for (int k = 0; k < 5; ++k)
       if (kG[a][k] != 0.f) s += kG[a][k] * in[k * S_IN];
     out[a * S_OUT] = s;
   }
+}
+
+template <int S_IN, int S_OUT>
+__host__ __device__ __forceinline__ void g6(const float* in, float* out) {
+  g6_rows<S_IN, S_OUT, 0, 6>(in, out);
 }
 
 // 2-D input transform of a 6x6 window (row-major, ld 6) -> 6x6
@@ -80,6 +85,19 @@ __host__ __device__ __forceinline__ void filter_tile(const float* g, float* u) {
   for (int kw = 0; kw < 5; ++kw) g6<5, 5>(g + kw, t + kw);  // t[a][kw] = sum_kh G[a][kh] g[kh][kw]
 #pragma unroll
   for (int a = 0; a < 6; ++a) g6<1, 1>(t + 5 * a, u + 6 * a);  // u[a][b] = sum_kw G[b][kw] t[a][kw]
+}
+
+// Rows a in [A0, A1) of filter_tile (u[6 a .. 6 a + 5]; the other rows of u
+// are not written): row a of u depends only on row a of kG, and each element
+// is formed by the expressions of filter_tile in the same order, so a
+// transform split by rows over several waves keeps every bit.
+template <int A0, int A1>
+__host__ __device__ __forceinline__ void filter_tile_rows(const float* g, float* u) {
+  float t[30];
+#pragma unroll
+  for (int kw = 0; kw < 5; ++kw) g6_rows<5, 5, A0, A1>(g + kw, t + kw);
+#pragma unroll
+  for (int a = A0; a < A1; ++a) g6<1, 1>(t + 5 * a, u + 6 * a);
 }
 
 // Output-transform weight of point (a, b) for output (i, j) of the 2x2 tile.
