@@ -225,7 +225,10 @@ def build_arg_parser(prog: str = "mpipy.py") -> argparse.ArgumentParser:
     d = TrainConfig()
     p.add_argument("--model", default=d.model, choices=MODELS)
     p.add_argument("--epochs", type=int, default=d.epochs, help="local epochs (mpipy.py:18)")
-    p.add_argument("--batch-size", type=int, default=d.batch_size)
+    p.add_argument("--batch-size", type=int, default=d.batch_size,
+                   help="rows per step and rank (mpipy.py:20), any positive size; the native "
+                        "MNIST engine computes ceil(B / 32) * 32 rows a step, the rows past B "
+                        "adding nothing to the gradients")
     p.add_argument("--dtype", default=d.dtype, choices=DTYPES)
     p.add_argument("--sync", default=d.sync, choices=SYNC_MODES)
     p.add_argument("--sync-every", type=int, default=d.sync_every)

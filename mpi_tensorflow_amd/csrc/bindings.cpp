@@ -743,7 +743,8 @@ PYBIND11_MODULE(_C, m) {
                                   RW(a1p) RW(a1t) RW(a2h) RW(a2t) RW(dy2p) RW(dy2t) RW(dh16)
                                       RW(dht16) RW(w1b) RW(w1t) RW(w2tb) RW(w2b) RW(a2_all)
                                           RW(dh_all) RW(hd_all) RW(dlog_all) RW(fac_ranks)
-                                              RW(wino) RW(wino_u) RW(wino_ud) RW(a2ft) RW(dp2);
+                                              RW(wino) RW(wino_u) RW(wino_ud) RW(a2ft) RW(dp2)
+                                                  RW(batch_pad);
 #undef RW
 
   py::class_<Collective>(m, "Collective")

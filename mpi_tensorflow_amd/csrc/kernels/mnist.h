@@ -38,12 +38,14 @@ struct C1FilterArgs {
   const float* da1m;
   const uint8_t* idx1;
   float* part1;
+  // logical batch of the data offset when `batch` is padded (0: = batch)
+  int lbatch = 0;
 };
 // out_pad (optional): zero-bordered NHWC copy [batch][18][18][32] of the pooled
 // output (its border is never written: allocate it zeroed)
 void launch_conv1_fwd(const float* data, const long long* step, int n_local, int batch,
                       const float* w, const float* b, float* out, uint8_t* argmax, hipStream_t s,
-                      float* out_pad = nullptr);
+                      float* out_pad = nullptr, int lbatch = 0);
 // bf16 engine: pooled conv1 output as zero-bordered bf16 images (see mnist_bf16.h);
 // with w1b != nullptr the same launch also re-derives the bf16 weight shadows
 // of the fp32 fc1 (w3) / conv2 (w2) weights (mnist_shared.h shadow_block)
@@ -52,7 +54,7 @@ void launch_conv1_fwd_bf16(const float* data, const long long* step, int n_local
                            uint8_t* argmax, int ld_batch, hipStream_t s,
                            const float* w3 = nullptr, const float* w2 = nullptr,
                            uint16_t* w1b = nullptr, uint16_t* w1t = nullptr,
-                           uint16_t* w2tb = nullptr, uint16_t* w2b = nullptr);
+                           uint16_t* w2tb = nullptr, uint16_t* w2b = nullptr, int lbatch = 0);
 // Train forward of conv1 + conv2 in ONE launch (fp32): every conv2 block
 // computes the pooled conv1 rows of its input halo itself (~2x recompute of the
 // 25-tap conv1) and writes the rows it owns to a1 / a1pf / idx1 (the layouts
@@ -66,6 +68,8 @@ struct C12In {
   float* a1 = nullptr;
   float* a1pf = nullptr;
   uint8_t* idx1 = nullptr;
+  // logical batch of the data offset when `batch` is padded (0: = batch)
+  int lbatch = 0;
 };
 void launch_conv12_fwd(const C12In& c1, int batch, const float* w2, const float* b2, float* a2,
                        uint8_t* idx2, float* w2t, hipStream_t s);
@@ -129,7 +133,11 @@ void launch_fc_head_train(const float* part, const float* b3, const float* w4, c
                           float keep_prob, uint32_t seed, uint32_t rank, float base_lr,
                           float lr_decay, float* hd, float* dh, float* dlog, float* loss_rows,
                           float* lr_out, int* correct, hipStream_t s, uint16_t* dh16 = nullptr,
-                          uint16_t* dht16 = nullptr, int splits = 14);  // slabs in part
+                          uint16_t* dht16 = nullptr, int splits = 14,  // slabs in part
+                          int lbatch = 0);
+// lbatch (padded step, 0: = batch): rows >= lbatch are pad rows - dlog / dh /
+// dh16 / dht16 exactly zero, loss_rows 0, not counted in `correct`; the valid
+// rows' dlog is scaled by 1 / lbatch and the offset and LR epoch use lbatch
 void launch_fc_head_eval(const float* h, const float* w4, const float* b4, const int* labels,
                          int M, float* logits, int* errors, hipStream_t s);
 // dY2 as NHWC dy2 [B][14][14][64] and (dy2t != nullptr: the direct
@@ -181,7 +189,8 @@ void set_xgmi_step_prof(unsigned long long* p);
 // p (2 x blocks u64; null turns them off)
 void set_conv2_bwd_wino_prof(unsigned long long* p);
 void launch_conv1_bwd_filter(const float* data, const long long* step, int n_local, int batch,
-                             const float* da1m, const uint8_t* idx1, float* part1, hipStream_t s);
+                             const float* da1m, const uint8_t* idx1, float* part1, hipStream_t s,
+                             int lbatch = 0);
 void launch_grad_finalize(const float* part2, int ngroups, const float* part1, int nblk1,
                           float* g_w2, float* g_b2, float* g_w1, float* g_b1, hipStream_t s);
 // The SGD launch that ends a train step (mnist.hip sgd_finalize_kernel):

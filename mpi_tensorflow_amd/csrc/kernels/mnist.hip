@@ -100,7 +100,8 @@ __global__ __launch_bounds__(64 * WM * WN * WK) void conv_pool_fwd_kernel(
     const float* __restrict__ data, const long long* step_ptr, int n_local, int batch,
     const float* __restrict__ w, const float* __restrict__ bias, float* __restrict__ out,
     uint8_t* __restrict__ argmax, __bf16* __restrict__ out_p, __bf16* __restrict__ out_t,
-    int ld_batch, float* __restrict__ out_pad, const ShadowPtrs sh, int conv_blocks) {
+    int ld_batch, float* __restrict__ out_pad, const ShadowPtrs sh, int conv_blocks,
+    int lbatch) {
   // out_p / out_t (bf16 engine, layouts in mnist_bf16.h): pooled output as
   // the zero-bordered K-packed image [C/16][ld_batch][PH+4][PW+4][16] and as
   // [n][PH+4][C][MNIST16_T_LD], instead of the fp32 NHWC `out`.  out_pad
@@ -119,7 +120,7 @@ __global__ __launch_bounds__(64 * WM * WN * WK) void conv_pool_fwd_kernel(
     shadow_block(bid - conv_blocks + (sh.w1b ? 0 : SHADOW_W1_BLOCKS), sh, smem);
     return;
   }
-  const long long off = batch_offset_dev(step_ptr, n_local, batch);
+  const long long off = batch_offset_dev(step_ptr, n_local, logical_batch(lbatch, batch));
   ConvPoolFwdProb<G> p{data + off * (G::H * G::W * G::CIN), w, batch};
   const int M = batch * G::PH * G::PW * 4;
   const int mt = (M + CF::BM - 1) / CF::BM;
@@ -292,14 +293,21 @@ __global__ __launch_bounds__(256) void fc_head_train_kernel(
     const long long* step_ptr, int batch, float keep_prob, uint32_t seed, uint32_t rank,
     float base_lr, float lr_decay, float* __restrict__ hd_out, float* __restrict__ dh_out,
     float* __restrict__ dlog_out, float* __restrict__ loss_rows, float* __restrict__ lr_out,
-    int* __restrict__ correct, __bf16* __restrict__ dh16, __bf16* __restrict__ dht16) {
+    int* __restrict__ correct, __bf16* __restrict__ dh16, __bf16* __restrict__ dht16,
+    int lbatch) {
   // dh16 / dht16 (bf16 engine): the K-packed MFMA operands of fc1 dX / dW1
+  // lbatch: the logical batch (schedule, 1 / B); `batch` rows are computed and
+  // strided.  Rows >= lbatch are pad rows: this is the one point where the
+  // backward pass is seeded, so their dlogits are exactly zero here and every
+  // later kernel sees zero factors for them.
   __shared__ float red[4][NCLS];
   __shared__ float dlog_s[NCLS];
   const int row = blockIdx.x;
   const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
   const long long step = step_ptr ? *step_ptr : 0;
-  const long long off = batch_offset_dev(step_ptr, n_local, batch);
+  const int lb = logical_batch(lbatch, batch);
+  const bool valid = row < lb;
+  const long long off = batch_offset_dev(step_ptr, n_local, lb);
   const uint32_t key = dropout_key(seed, rank, (uint32_t)step, 0u);
   const float scale = 1.f / keep_prob;
   // the label and fc2 bias used after the logit reduction: loaded now, not
@@ -350,14 +358,14 @@ __global__ __launch_bounds__(256) void fc_head_train_kernel(
     const float se = wave_sum(e);
     const float p = e / se;
     const float lab_logit = wave_sum(lane == label ? logit : 0.f);
-    if (lane < NCLS) dlog_s[lane] = (p - (lane == label ? 1.f : 0.f)) / (float)batch;
+    if (lane < NCLS) dlog_s[lane] = valid ? (p - (lane == label ? 1.f : 0.f)) / (float)lb : 0.f;
     const unsigned long long bal = __ballot(lane < NCLS && logit == mx);
     const int am = __ffsll((long long)bal) - 1;
     if (lane == 0) {
-      loss_rows[row] = (logf(se) + mx) - lab_logit;  // logsumexp - logit[label]
-      if (correct) atomicAdd(correct, am == label ? 1 : 0);
+      loss_rows[row] = valid ? (logf(se) + mx) - lab_logit : 0.f;  // logsumexp - logit[label]
+      if (correct && valid) atomicAdd(correct, am == label ? 1 : 0);
       if (row == 0 && lr_out) {
-        const float e2 = (float)((step * batch) / n_local);
+        const float e2 = (float)((step * lb) / n_local);
         lr_out[0] = base_lr * powf(lr_decay, e2);
       }
     }
@@ -373,7 +381,7 @@ __global__ __launch_bounds__(256) void fc_head_train_kernel(
     float d = 0.f;
 #pragma unroll
     for (int c = 0; c < NCLS; ++c) d += dl[c] * w4r[u][c];
-    d = (kp[u] && z[u] > 0.f) ? d * scale : 0.f;
+    d = (kp[u] && z[u] > 0.f) ? d * scale : 0.f;  // pad row: dl == 0, so d == +0.f
     hd_out[row * FC1_OUT + j] = hd[u];
     dh_out[row * FC1_OUT + j] = d;
     if (dh16) {  // K-packed layouts of mnist_bf16.h
@@ -745,7 +753,7 @@ template <int NT, class Sink>
 __device__ __forceinline__ void conv1_into_halo_t(const C12In& c1, int batch, int n, int pg,
                                                   float* __restrict__ img, const Sink& sink) {
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  const long long off = batch_offset_dev(c1.step, c1.n_local, batch);
+  const long long off = batch_offset_dev(c1.step, c1.n_local, logical_batch(c1.lbatch, batch));
   const float* xin = c1.data + (off + n) * 784;
   const int iy0 = 8 * pg - 6;
   constexpr int NIMG = C12_IMG_ROWS * C12_IMG_LD;  // 660
@@ -1615,7 +1623,7 @@ __device__ __forceinline__ void bwd_data_wino_block(
                   ci];
   }
   if (do_c1) {
-    const long long off = batch_offset_dev(c1.step, c1.n_local, batch);
+    const long long off = batch_offset_dev(c1.step, c1.n_local, logical_batch(c1.lbatch, batch));
     const float* x = c1.data + (off + n) * 784;
     const int y0 = 8 * pg - 2;
     if (tid < C1X) {
@@ -2493,20 +2501,20 @@ static inline int cdiv(int a, int b) { return (a + b - 1) / b; }
 
 void launch_conv1_fwd(const float* data, const long long* step, int n_local, int batch,
                       const float* w, const float* b, float* out, uint8_t* argmax,
-                      hipStream_t s, float* out_pad) {
+                      hipStream_t s, float* out_pad, int lbatch) {
   const int M = batch * 14 * 14 * 4;
   const int mt = cdiv(M, 32 * C1_WM), nt = 32 / (32 * C1_WN);
   conv_pool_fwd_kernel<Conv1, C1_WM, C1_WN, C1_WK>
       <<<mt * nt, 64 * C1_WM * C1_WN * C1_WK, 0, s>>>(data, step, n_local, batch, w, b, out,
                                                       argmax, nullptr, nullptr, 0, out_pad,
-                                                      ShadowPtrs{}, mt * nt);
+                                                      ShadowPtrs{}, mt * nt, lbatch);
 }
 
 void launch_conv1_fwd_bf16(const float* data, const long long* step, int n_local, int batch,
                            const float* w, const float* b, uint16_t* a1p, uint16_t* a1t,
                            uint8_t* argmax, int ld_batch, hipStream_t s, const float* w3,
                            const float* w2, uint16_t* w1b, uint16_t* w1t, uint16_t* w2tb,
-                           uint16_t* w2b) {
+                           uint16_t* w2b, int lbatch) {
   const int M = batch * 14 * 14 * 4;
   const int mt = cdiv(M, 32 * C1_WM), nt = 32 / (32 * C1_WN);
   auto B16 = [](uint16_t* p) { return reinterpret_cast<__bf16*>(p); };
@@ -2516,7 +2524,7 @@ void launch_conv1_fwd_bf16(const float* data, const long long* step, int n_local
   conv_pool_fwd_kernel<Conv1, C1_WM, C1_WN, C1_WK>
       <<<mt * nt + extra, 64 * C1_WM * C1_WN * C1_WK, 0, s>>>(
           data, step, n_local, batch, w, b, nullptr, argmax, B16(a1p), B16(a1t), ld_batch, nullptr,
-          sh, mt * nt);
+          sh, mt * nt, lbatch);
 }
 
 void launch_conv2_fwd(const float* a1, int batch, const float* w, const float* b, float* out,
@@ -2591,13 +2599,14 @@ void launch_fc_head_train(const float* part, const float* b3, const float* w4, c
                           float keep_prob, uint32_t seed, uint32_t rank, float base_lr,
                           float lr_decay, float* hd, float* dh, float* dlog, float* loss_rows,
                           float* lr_out, int* correct, hipStream_t s, uint16_t* dh16,
-                          uint16_t* dht16, int splits) {
+                          uint16_t* dht16, int splits, int lbatch) {
+  if (lbatch < 0 || lbatch > batch) throw std::runtime_error("fc_head_train: lbatch > batch");
 #define HEAD(NS_)                                                                              \
   fc_head_train_kernel<NS_><<<batch, 256, 0, s>>>(part, b3, w4, b4, labels, n_local, step, batch, \
                                                   keep_prob, seed, rank, base_lr, lr_decay, hd, dh, \
                                                   dlog, loss_rows, lr_out, correct,              \
                                                   reinterpret_cast<__bf16*>(dh16),               \
-                                                  reinterpret_cast<__bf16*>(dht16))
+                                                  reinterpret_cast<__bf16*>(dht16), lbatch)
   if (splits == FC1T_SPLITS)
     HEAD(FC1T_SPLITS);
   else if (splits == FC1_SPLITS)
@@ -2807,14 +2816,14 @@ void launch_conv2_bwd_filter_wino_prof(const float* a1p, const float* dy2, int b
 
 C1Filter c1_args(const C1FilterArgs* a) {
   if (a == nullptr) return C1Filter{};
-  return C1Filter{a->data, a->step, a->n_local, a->da1m, a->idx1, a->part1};
+  return C1Filter{a->data, a->step, a->n_local, a->da1m, a->idx1, a->part1, a->lbatch};
 }
 
 void launch_conv1_bwd_filter(const float* data, const long long* step, int n_local, int batch,
                              const float* da1m, const uint8_t* idx1, float* part1,
-                             hipStream_t s) {
+                             hipStream_t s, int lbatch) {
   conv1_bwd_filter_kernel<<<conv1_filter_blocks(batch), 256, 0, s>>>(
-      batch, C1Filter{data, step, n_local, da1m, idx1, part1});
+      batch, C1Filter{data, step, n_local, da1m, idx1, part1, lbatch});
 }
 
 // ------------------------------------------------- SGD of the step ----

@@ -506,7 +506,8 @@ __device__ __forceinline__ void c2b_data_block(int db, const bf* __restrict__ dy
   if (conv1) {
     if (tid < C2B_PIX * 4 && pbase + (tid >> 2) < M)
       qv = *reinterpret_cast<const uint2*>(c1.idx1 + (size_t)pbase * 32 + 8 * tid);
-    const long long off = mnist::batch_offset_dev(c1.step, c1.n_local, batch);
+    const long long off = mnist::batch_offset_dev(c1.step, c1.n_local,
+                                                   mnist::logical_batch(c1.lbatch, batch));
 #pragma unroll
     for (int j = 0; j < XJ; ++j) {
       const int i = tid + 512 * j;

@@ -18,6 +18,13 @@ __device__ __forceinline__ long long batch_offset_dev(const long long* step_ptr,
   return (s * batch) % (long long)(n_local - batch);
 }
 
+// The step may run on a batch padded to whole 32-image tiles: strides, grids
+// and slab counts take the padded `batch`, the schedule (batch offset, LR
+// epoch, the 1 / B of the mean loss) the logical one.  lbatch == 0: no padding.
+__host__ __device__ __forceinline__ int logical_batch(int lbatch, int batch) {
+  return lbatch > 0 ? lbatch : batch;
+}
+
 // fc2 weight / bias and fc1 bias grads (B1, B2): dW4 = hd^T dlog, db4 = sum
 // dlog, db3 = sum dh.  Block blk owns hidden units [64 blk, 64 blk + 64); its
 // 4 waves take every 4th row.  dlog is staged in LDS 64 rows at a time (one
@@ -113,6 +120,7 @@ struct C1Filter {  // conv1 filter-grad role arguments (part1 == nullptr: off)
   const float* da1m;
   const uint8_t* idx1;
   float* part1;
+  int lbatch;  // logical batch of the offset (0: = batch)
 };
 
 C1Filter c1_args(const C1FilterArgs* a);  // host (mnist.hip)
@@ -125,7 +133,7 @@ __device__ inline void conv1_filter_unit(int unit, int batch, const C1Filter& c,
   float* xs = smem;            // rows 2*PR*band-2 .. +XR-1 of the padded image
   float* red = smem + XR * 32;  // [NW][26 * 32 + 1]
   const int n = unit / SPLIT, band = unit % SPLIT;
-  const long long off = batch_offset_dev(c.step, c.n_local, batch);
+  const long long off = batch_offset_dev(c.step, c.n_local, logical_batch(c.lbatch, batch));
   const float* x = c.data + (off + n) * 784;
   const int tid = threadIdx.x, co = tid & 31, grp = tid >> 5, wave = tid >> 6;
   const int y0 = 2 * PR * band - 2;  // first image row held in xs

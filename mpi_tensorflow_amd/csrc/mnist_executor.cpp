@@ -18,10 +18,13 @@ static inline T* P(uintptr_t v) {
 }
 
 MnistExecutor::MnistExecutor(const MnistPtrs& p) : p_(p) {
-  if (p_.batch <= 0 || p_.batch % 32 != 0)
-    throw std::runtime_error("MnistExecutor: batch must be a positive multiple of 32");
+  if (p_.batch <= 0) throw std::runtime_error("MnistExecutor: batch must be positive");
   if (p_.n_local <= p_.batch)
     throw std::runtime_error("MnistExecutor: local shard must exceed the batch");
+  const int padded = (p_.batch + 31) / 32 * 32;
+  if (p_.batch_pad == 0) p_.batch_pad = padded;
+  if (p_.batch_pad != padded)
+    throw std::runtime_error("MnistExecutor: batch_pad must be the batch rounded up to 32");
   if (p_.total % 4 != 0 || p_.l2_end % 4 != 0 || p_.bucket1 % 4 != 0 || p_.l2_end > p_.bucket1)
     throw std::runtime_error(
         "MnistExecutor: flat segments must be multiples of 4 floats with the L2 prefix in bucket 1");
@@ -55,7 +58,7 @@ void MnistExecutor::enqueue_fwd_bwd(hipStream_t s, bool finalize,
   float* W = P<float>(p.params);
   float* G = P<float>(p.grads);
   const long long* step = P<const long long>(p.step);
-  const int B = p.batch;
+  const int B = p.batch_pad;  // rows computed; p.batch: the schedule's batch
   // forward
   // conv1 is recomputed inside the conv2 blocks (one launch, ~3 us less than a
   // separate conv1 launch staging a1 through memory: 108.2 -> 105.0 us/step)
@@ -63,6 +66,7 @@ void MnistExecutor::enqueue_fwd_bwd(hipStream_t s, bool finalize,
   cf.data = P<const float>(p.train_x);
   cf.step = step;
   cf.n_local = p.n_local;
+  cf.lbatch = p.batch;
   cf.w1 = W + p.off_w1;
   cf.b1 = W + p.off_b1;
   // compact Winograd backward (MnistPtrs::dp2): no a1 / dy2 / da1m buffers
@@ -93,7 +97,8 @@ void MnistExecutor::enqueue_fwd_bwd(hipStream_t s, bool finalize,
                               p.keep_prob, p.seed, p.rank, p.base_lr, p.lr_decay, P<float>(p.hd),
                               P<float>(p.dh), P<float>(p.dlog), P<float>(p.loss_rows),
                               P<float>(p.lr), P<int>(p.correct), s, nullptr, nullptr,
-                              fc1_t ? mnist::fc1_train_t_splits() : mnist::fc1_train_splits());
+                              fc1_t ? mnist::fc1_train_t_splits() : mnist::fc1_train_splits(),
+                              p.batch);
   if (factors && sched_ == SCHED_FACTORS) HIP_CHECK(hipEventRecord(ev_fac_, s));
   // backward: fc1 dX (+pool2/ReLU2 scatter) | dW1 | fc2 grads, one launch
   // (SCHED_XGMI_FAC: dX | the peers' factor rows over the links)
@@ -116,7 +121,7 @@ void MnistExecutor::enqueue_fwd_bwd(hipStream_t s, bool finalize,
   // dA1 values they produce; direct - role blocks of the filter-grad launch
   const mnist::C1FilterArgs c1{P<const float>(p.train_x), step, p.n_local,
                                P<const float>(p.da1m), P<const uint8_t>(p.idx1),
-                               P<float>(p.part1)};
+                               P<float>(p.part1), p.batch};
   if (compact) {
     // dp2 + idx2 instead of dy2, the ReLU1 mask from a1pf, no dA1 store (the
     // conv1 filter gradient is formed in the bwd-data blocks: c1.part1)
@@ -162,7 +167,7 @@ void MnistExecutor::enqueue_fwd_bwd_bf16(hipStream_t s, bool finalize,
   float* W = P<float>(p.params);
   float* G = P<float>(p.grads);
   const long long* step = P<const long long>(p.step);
-  const int B = p.batch;
+  const int B = p.batch_pad;  // rows computed; p.batch: the schedule's batch
   using U16 = uint16_t;
   if (shadows_fresh && B % 16 == 0) {
     // every shadow is current (the previous step's SGD launch, or
@@ -172,6 +177,7 @@ void MnistExecutor::enqueue_fwd_bwd_bf16(hipStream_t s, bool finalize,
     cf.data = P<const float>(p.train_x);
     cf.step = step;
     cf.n_local = p.n_local;
+    cf.lbatch = p.batch;
     cf.w1 = W + p.off_w1;
     cf.b1 = W + p.off_b1;
     cf.idx1 = P<uint8_t>(p.idx1);
@@ -188,7 +194,7 @@ void MnistExecutor::enqueue_fwd_bwd_bf16(hipStream_t s, bool finalize,
                                  W + p.off_b1, P<U16>(p.a1p), P<U16>(p.a1t), P<uint8_t>(p.idx1),
                                  B, s, W + p.off_w3, W + p.off_w2,
                                  w1_done ? nullptr : P<U16>(p.w1b), P<U16>(p.w1t), P<U16>(p.w2tb),
-                                 P<U16>(p.w2b));
+                                 P<U16>(p.w2b), p.batch);
     mnist16::launch_conv2_fwd(P<const U16>(p.a1p), B, P<const U16>(p.w2tb), W + p.off_b2,
                               P<U16>(p.a2h), P<U16>(p.a2t), P<uint8_t>(p.idx2), s);
   }
@@ -199,7 +205,7 @@ void MnistExecutor::enqueue_fwd_bwd_bf16(hipStream_t s, bool finalize,
                               p.keep_prob, p.seed, p.rank, p.base_lr, p.lr_decay, P<float>(p.hd),
                               P<float>(p.dh), P<float>(p.dlog), P<float>(p.loss_rows),
                               P<float>(p.lr), P<int>(p.correct), s, P<U16>(p.dh16),
-                              P<U16>(p.dht16));
+                              P<U16>(p.dht16), mnist::fc1_train_splits(), p.batch);
   mnist16::launch_fc1_bwd(P<const U16>(p.a2h), P<const U16>(p.a2t), P<const uint8_t>(p.idx2),
                           P<const U16>(p.dh16), P<const U16>(p.dht16), P<const float>(p.hd),
                           P<const float>(p.dh), P<const float>(p.dlog), P<const U16>(p.w1b), B,
@@ -209,7 +215,7 @@ void MnistExecutor::enqueue_fwd_bwd_bf16(hipStream_t s, bool finalize,
   // conv2 bwd-data (+ conv1 filter grad) | conv2 filter grad | FC SGD: one launch
   const mnist::C1FilterArgs c1{P<const float>(p.train_x), step, p.n_local,
                                P<const float>(p.da1m), P<const uint8_t>(p.idx1),
-                               P<float>(p.part1)};
+                               P<float>(p.part1), p.batch};
   static const bool lab_split = [] {  // lab (MTA_C2B_LAB=3): the two-launch form
     const char* e = getenv("MTA_C2B_LAB");
     return e && atoi(e) == 3;
@@ -231,9 +237,9 @@ void MnistExecutor::enqueue_fwd_bwd_bf16(hipStream_t s, bool finalize,
 }
 
 int MnistExecutor::conv2_groups() const {
-  if (p_.bf16) return mnist16::conv2_filter_groups(p_.batch);
-  return p_.wino ? mnist::conv2_wino_filter_groups(p_.batch)
-                 : mnist::conv2_filter_splits(p_.batch);
+  if (p_.bf16) return mnist16::conv2_filter_groups(p_.batch_pad);
+  return p_.wino ? mnist::conv2_wino_filter_groups(p_.batch_pad)
+                 : mnist::conv2_filter_splits(p_.batch_pad);
 }
 
 // the Winograd bwd-data blocks produce one conv1 partial per band of 4 a1 rows,
@@ -241,10 +247,10 @@ int MnistExecutor::conv2_groups() const {
 int MnistExecutor::conv1_blocks() const {
   if (p_.bf16) {
     const char* e = getenv("MTA_C2B_LAB");
-    if (e && atoi(e) == 3) return mnist::conv1_filter_blocks(p_.batch, 7);
-    return mnist16::conv2_bwd_conv1_rows(p_.batch);
+    if (e && atoi(e) == 3) return mnist::conv1_filter_blocks(p_.batch_pad, 7);
+    return mnist16::conv2_bwd_conv1_rows(p_.batch_pad);
   }
-  return mnist::conv1_filter_blocks(p_.batch, p_.wino ? 4 : 7);
+  return mnist::conv1_filter_blocks(p_.batch_pad, p_.wino ? 4 : 7);
 }
 
 void MnistExecutor::forward_backward(hipStream_t s) {
@@ -383,7 +389,7 @@ bool MnistExecutor::xgmi_fac_ok() const {
   const int n = xgmi_->size();
   if (n < 2 || n != p_.fac_ranks || !p_.a2_all || !p_.dh_all || !p_.hd_all || !p_.dlog_all)
     return false;
-  const size_t B = (size_t)p_.batch;
+  const size_t B = (size_t)p_.batch_pad;
   return xgmi_->registered(P<const void>(p_.a2_all), n * B * kFc1In * sizeof(float)) &&
          xgmi_->registered(P<const void>(p_.dh_all), n * B * kFc1Out * sizeof(float)) &&
          xgmi_->registered(P<const void>(p_.hd_all), n * B * kFc1Out * sizeof(float)) &&
@@ -439,7 +445,7 @@ void MnistExecutor::train_step(hipStream_t s, Collective* comm, hipStream_t cs,
     if (fuse_dw1) {
       fc.a2 = P<const float>(p.a2);
       fc.dh = P<const float>(p.dh);
-      fc.batch = p.batch;
+      fc.batch = p.batch_pad;  // (the pad rows' dh are zero)
       fc.w1 = p.off_w3;
     }
     const bool role = fc.rounds > 0;
@@ -633,7 +639,7 @@ void MnistExecutor::train_step_factors(hipStream_t s, Collective* comm, hipStrea
   const MnistPtrs& p = p_;
   float* G = P<float>(p.grads);
   const int n = comm->size(), r = comm->rank();
-  const size_t B = (size_t)p.batch;
+  const size_t B = (size_t)p.batch_pad;  // factor rows a rank (pad rows: zero dh / dlog)
   const float gscale = 1.0f / (float)n;
   const bool fused = fused_sgd_ok();
   enqueue_fwd_bwd(s, /*finalize=*/true, nullptr, /*factors=*/true, take_fresh(fused));
@@ -657,7 +663,7 @@ void MnistExecutor::train_step_factors(hipStream_t s, Collective* comm, hipStrea
   // measured slower with per-element update chains and neutral with all
   // loads batched first, docs/PERF_NOTES.md)
   HIP_CHECK(hipStreamWaitEvent(s, ev_b1_, 0));
-  mnist::launch_fc1_bwd_weights(a2, dh, hd, dl, n * p.batch, G + p.off_w3, G + p.off_b3,
+  mnist::launch_fc1_bwd_weights(a2, dh, hd, dl, n * p.batch_pad, G + p.off_w3, G + p.off_b3,
                                 G + p.off_w4, G + p.off_b4, s);
   HIP_CHECK(hipStreamWaitEvent(s, ev_done_, 0));
   if (fused)
@@ -790,7 +796,7 @@ void MnistExecutor::train_step_xgmi_fac(hipStream_t s) {
   wait_fc_params(s);
   mnist::XgmiFacArgs f;
   f.sync = x->sync();
-  const size_t B = (size_t)p.batch;
+  const size_t B = (size_t)p.batch_pad;  // factor rows a rank (pad rows: zero dh / dlog)
   const uintptr_t bufs[4] = {p.a2_all, p.dh_all, p.hd_all, p.dlog_all};
   const size_t rows[4] = {B * kFc1In, B * kFc1Out, B * kFc1Out, B * kNcls};
   for (int k = 0; k < 4; ++k) {
@@ -806,13 +812,13 @@ void MnistExecutor::train_step_xgmi_fac(hipStream_t s) {
   // and applied by the step launch's FC tiles
   float* G = P<float>(p.grads);
   mnist::launch_fc1_small_grads(P<const float>(p.dh_all), P<const float>(p.hd_all),
-                                P<const float>(p.dlog_all), n * p.batch, G + p.off_b3,
+                                P<const float>(p.dlog_all), n * p.batch_pad, G + p.off_b3,
                                 G + p.off_w4, G + p.off_b4, s);
   mnist::XgmiStepArgs a = xgmi_step_args();
   a.fc_local = 1;
   a.fa2 = P<const float>(p.a2_all);
   a.fdh = P<const float>(p.dh_all);
-  a.frows = n * p.batch;
+  a.frows = n * p.batch_pad;
   a.off_w3 = (int)p.off_w3;
   mnist::launch_xgmi_step(a, s);
 }

@@ -34,6 +34,15 @@ struct MnistPtrs {
   // dataset (device resident)
   uintptr_t train_x = 0, train_y = 0;
   int n_local = 0, batch = 64;
+  // `batch` is the logical batch B (any size): the batch offset, the LR epoch
+  // and the 1 / B of the mean loss.  The kernels tile the batch in groups of
+  // 32 images, so the step computes batch_pad = ceil(B / 32) * 32 rows (0:
+  // derived); every activation / factor / slab buffer below is sized and
+  // strided by batch_pad, and train_x / train_y carry batch_pad - batch zero
+  // rows past n_local (the pad rows read them).  The head kernel seeds the
+  // backward pass with exact zeros for the pad rows, so they add nothing to
+  // any gradient.
+  int batch_pad = 0;
   // flat buffers
   uintptr_t params = 0, grads = 0, mom = 0;
   long long total = 0, l2_end = 0, bucket1 = 0;  // floats
@@ -61,7 +70,7 @@ struct MnistPtrs {
   int grad_bf16 = 0;
   uintptr_t gb16 = 0;
   // SCHED_FACTORS (fp32, world > 1): rank-major gathered FC factors of all
-  // ranks, [world * batch] rows each (a2 [.][3136], dh / hd [.][512], dlog
+  // ranks, [world * batch_pad] rows each (a2 [.][3136], dh / hd [.][512], dlog
   // [.][10]); a2 / dh / hd / dlog above point at this rank's slot in them
   uintptr_t a2_all = 0, dh_all = 0, hd_all = 0, dlog_all = 0;
   int fac_ranks = 0;  // communicator size the factor buffers were sized for

@@ -202,17 +202,30 @@ class NativeMnistEngine(MnistEngineBase):
             self.grad_sync = True
         if device.type != "cuda":
             raise RuntimeError("NativeMnistEngine needs a GPU")
-        if self.B % 32 != 0:
-            raise ValueError("native MNIST engine needs a batch size that is a multiple of 32")
         C_ = native()
         self._C = C_
         dev = device
-        B = self.B
+        # The kernels tile the batch in groups of 32 images: the step computes
+        # Bp = ceil(B / 32) * 32 rows.  The head kernel seeds the backward pass
+        # with exact zeros for the Bp - B pad rows, so they add nothing to any
+        # gradient; the offset, the LR and the mean loss use the logical
+        # self.B.  Every buffer below is sized by Bp (local name B).
+        self.Bp = (self.B + 31) // 32 * 32
+        B = self.Bp
         f32 = dict(dtype=torch.float32, device=dev)
         u8 = dict(dtype=torch.uint8, device=dev)
-        self.train_x = torch.from_numpy(np.ascontiguousarray(train_x, np.float32)).to(dev)
-        self.train_y = torch.from_numpy(np.ascontiguousarray(train_y).astype(np.int32)).to(dev)
-        assert self.train_x.shape[1:] == (28, 28, 1)
+        # the pad rows read the shard at offset + row, up to Bp - B rows past
+        # its end: trailing zero images with label 0 keep those reads in bounds
+        # (n_local stays the real row count)
+        pad = self.Bp - self.B
+        tx = torch.from_numpy(np.ascontiguousarray(train_x, np.float32))
+        ty = torch.from_numpy(np.ascontiguousarray(train_y).astype(np.int32))
+        assert tx.shape[1:] == (28, 28, 1)
+        if pad:
+            tx = torch.cat([tx, torch.zeros((pad,) + tuple(tx.shape[1:]), dtype=tx.dtype)])
+            ty = torch.cat([ty, torch.zeros(pad, dtype=ty.dtype)])
+        self.train_x = tx.to(dev)
+        self.train_y = ty.to(dev)
         self.step_dev = torch.zeros(1, dtype=torch.int64, device=dev)
         self.lr_dev = torch.zeros(1, **f32)
         self.correct_dev = torch.zeros(1, dtype=torch.int32, device=dev)
@@ -280,7 +293,7 @@ class NativeMnistEngine(MnistEngineBase):
                 self.bufs[name] = torch.empty(0, **f32)
         p = C_.MnistPtrs()
         p.train_x, p.train_y = ptr(self.train_x), ptr(self.train_y)
-        p.n_local, p.batch = self.n_local, B
+        p.n_local, p.batch, p.batch_pad = self.n_local, self.B, self.Bp
         p.params, p.grads, p.mom = ptr(self.params), ptr(self.grads), ptr(self.mom)
         lay = self.layout
         p.total = lay.total
@@ -717,7 +730,9 @@ class NativeMnistEngine(MnistEngineBase):
         self.exe.forward_backward(stream_handle())
 
     def loss_value(self) -> float:
-        return float(self.bufs["loss_rows"].mean().item()) + self.l2_value()
+        rows = self.bufs["loss_rows"]  # [Bp]; the mean is over the B real rows
+        data = rows.mean().item() if self.Bp == self.B else rows[:self.B].sum().item() / self.B
+        return float(data) + self.l2_value()
 
     def device_lr(self) -> float:
         return float(self.lr_dev.item())
