@@ -135,6 +135,9 @@ class TrainConfig:
     data_dir: str = "data"
     synthetic: Optional[bool] = None  # None = use real files if present
     download: bool = False
+    # a new row order for every pass over the local shard (runtime/shuffle.py);
+    # off = the reference's file order (mpipy.py:80), the same batches every pass
+    shuffle: bool = False
     # learning rate / optimiser
     base_lr: float = BASE_LR
     lr_decay: float = LR_DECAY
@@ -261,6 +264,9 @@ def build_arg_parser(prog: str = "mpipy.py") -> argparse.ArgumentParser:
     g.add_argument("--synthetic", dest="synthetic", action="store_true", default=None)
     g.add_argument("--real-data", dest="synthetic", action="store_false")
     p.add_argument("--download", action="store_true", help="try DATA_URL if files missing")
+    p.add_argument("--shuffle", action="store_true",
+                   help="permute each rank's shard anew for every pass (on the device, a pure "
+                        "function of seed, rank and pass; the reference reads in file order)")
     p.add_argument("--base-lr", type=float, default=d.base_lr)
     p.add_argument("--lr-decay", type=float, default=d.lr_decay)
     p.add_argument("--momentum", type=float, default=d.momentum)

@@ -14,6 +14,7 @@
 #include "kernels/mnist.h"
 #include "kernels/mnist_bf16.h"
 #include "kernels/ops_generic.h"
+#include "kernels/shuffle.h"
 #include "lenet_executor.h"
 #include "mnist_executor.h"
 #include "rccl_comm.h"
@@ -729,6 +730,17 @@ PYBIND11_MODULE(_C, m) {
   }, py::arg("data"), py::arg("labels"), py::arg("step"), py::arg("n_local"), py::arg("batch"),
      py::arg("row_elems"), py::arg("xb"), py::arg("yb"), py::arg("st"), py::arg("lr_base") = 0.f,
      py::arg("lr_decay") = 1.f, py::arg("lr_out") = 0);
+  // per-pass row shuffle of the device-resident shard (kernels/shuffle.h)
+  g.def("shuffle_rows", [](uintptr_t src_x, uintptr_t src_y, uintptr_t dst_x, uintptr_t dst_y,
+                           long long n, long long row_elems, uint32_t key, uintptr_t st) {
+    shuffle::shuffle_rows(P<const float>(src_x), P<const int>(src_y), P<float>(dst_x), P<int>(dst_y),
+                          n, row_elems, key, S(st));
+    check_launch();
+  });
+  g.def("shuffle_perm", [](uintptr_t out, long long n, uint32_t key, uintptr_t st) {
+    shuffle::shuffle_perm(P<int>(out), n, key, S(st));
+    check_launch();
+  });
 
   // ------------------------------------------------------------ executor
   py::class_<MnistPtrs>(m, "MnistPtrs")

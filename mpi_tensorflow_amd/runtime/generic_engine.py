@@ -44,6 +44,7 @@ from ..parallel.overlap import BUCKET_PLANS, BucketedAllReduce, SegmentedStep, p
 from ..utils.data import batch_offset
 from ..utils.devcache import DeviceArrayCache
 from ..utils.schedule import learning_rate
+from .shuffle import make_shuffler
 
 
 class _null:
@@ -135,6 +136,14 @@ class GenericEngine:
             if self.wcache.njobs == 0:  # (LeNet-5 etc.: nothing to keep)
                 self.wcache = None
             self._wfresh = False  # the copies match the fp32 weights
+        # cfg.shuffle: the per-pass row order of train_x / train_y (runtime/shuffle.py;
+        # keyed by the rank of the dropout stream, Q14): the HIP gather on the
+        # native path, the host permutation on the PyTorch paths
+        self.shuffler = make_shuffler(cfg, 0 if cfg.same_seed_all_ranks else rank, self.n_local,
+                                      self.train_x, self.train_y,
+                                      native=self._C if self.on_gpu else None)
+        if self.shuffler is not None:
+            self.train_x, self.train_y = self.shuffler.work_x, self.shuffler.work_y
 
     # ------------------------------------------------------------------ util
     @property
@@ -178,6 +187,8 @@ class GenericEngine:
         from ..parallel import dist as D
         G = self.graph_steps
         host_step = self.step
+        if self.shuffler is not None:  # the (discarded) trial steps read the current pass
+            self.shuffler.ensure(self.step)
         snap = (self.params.detach().clone(), self.mom.clone(), self.step_dev.clone(),
                 {k: (rm.clone(), rv.clone()) for k, (rm, rv) in self.bn.items()})
         self._warmup(3)  # the capture precondition; its steps are undone below too
@@ -265,6 +276,8 @@ class GenericEngine:
         update must apply (1/world when the grads hold a cross-rank sum).
         Public entry (tests, serial emulations): the caller may have changed
         the weights, so the conv weight copies are re-derived first."""
+        if self.shuffler is not None:
+            self.shuffler.ensure(self.step)
         if self.wcache is not None:
             self.wcache.refresh()
             self._wfresh = True
@@ -323,6 +336,8 @@ class GenericEngine:
                               ptr(self.step_dev), s)
 
     def _step_cpu(self):
+        if self.shuffler is not None:
+            self.shuffler.ensure(self.step)
         off = batch_offset(self.step, self.n_local, self.B)
         x = self.train_x[off:off + self.B]
         y = self.train_y[off:off + self.B]
@@ -449,7 +464,9 @@ class GenericEngine:
         s = torch.cuda.Stream()
         s.wait_stream(torch.cuda.current_stream())
         with torch.cuda.stream(s):
-            for _ in range(n):
+            for i in range(n):
+                if self.shuffler is not None:  # (callers other than train may cross a pass)
+                    self.shuffler.ensure(self.step + i)
                 self._step_gpu()
         torch.cuda.current_stream().wait_stream(s)
         self._warm = True
@@ -470,6 +487,14 @@ class GenericEngine:
             self._graph(k % G)
 
     def train(self, k: int) -> None:
+        if self.shuffler is None or not self.on_gpu:  # (the CPU step checks its pass itself)
+            return self._train(k)
+        # k is cut at the pass boundaries here, whatever the caller asked for
+        for p, m in self.shuffler.segments(self.step, k):
+            self.shuffler.load(p)
+            self._train(m)
+
+    def _train(self, k: int) -> None:
         if k <= 0:
             return
         if not self.on_gpu:

@@ -25,6 +25,7 @@ from ..ops import native, ptr, stream_handle
 from ..parallel.comm import DeviceComm, XgmiDeviceComm
 from ..utils.devcache import DeviceArrayCache
 from ..utils.schedule import learning_rate
+from .shuffle import make_shuffler
 
 # the executor's xGMI sync modes (csrc/lenet_executor.h XGMI_*)
 XGMI_MODES = C.XGMI_MODES
@@ -79,6 +80,10 @@ class NativeLenetEngine:
             self.grad_sync = True
         C_ = native()
         self._C = C_
+        # cfg.shuffle: the per-pass row order of the working copy above
+        # (runtime/shuffle.py; keyed by the rank of the dropout stream, Q14)
+        self.shuffler = make_shuffler(cfg, 0 if cfg.same_seed_all_ranks else rank, self.n_local,
+                                      self.train_x, self.train_y, native=C_)
         na, nd, nc = C_.lenet_buffer_floats(self.B)
         self.acts = torch.zeros(na, device=dev)
         self.deltas = torch.zeros(nd, device=dev)
@@ -241,6 +246,8 @@ class NativeLenetEngine:
         from ..parallel.sync import replicas_identical
         from .mnist_engine import TUNE_REPLAYS, XGMI_STEP_RTOL
         G = self.graph_steps
+        if self.shuffler is not None:  # the (discarded) trial steps read the current pass
+            self.shuffler.ensure(self.step)
         snap = (self.params.clone(), self.mom.clone(), self.step_dev.clone())
         xh = self.xcomm.native_handle
         cands = [("all-reduce", self._native_comm, "two-phase"), ("xgmi", xh, "two-phase"),
@@ -334,6 +341,16 @@ class NativeLenetEngine:
             return
         if not self._tuned:  # side-effect free: restores the state it trained
             self.tune_schedule()
+        if self.shuffler is None:
+            self._run_steps(k)
+        else:  # k is cut at the pass boundaries here, whatever the caller asked for
+            for p, m in self.shuffler.segments(self.step, k):
+                self.shuffler.load(p)
+                self._run_steps(m)
+        self.step += k
+
+    def _run_steps(self, k: int) -> None:
+        """k steps on the shard as it stands: graph replays, else eager launches."""
         done = 0
         if self.use_graph:
             G = self.graph_steps
@@ -350,11 +367,12 @@ class NativeLenetEngine:
                     done += rem
         for _ in range(k - done):
             self._launch_one()
-        self.step += k
 
     def forward_backward_only(self) -> None:
         """Forward + backward, weight grads into the flat grad buffer (no
         sync, no SGD, no step increment): numerics tests."""
+        if self.shuffler is not None:
+            self.shuffler.ensure(self.step)
         self.exe.forward_backward(stream_handle())
 
     # ------------------------------------------------------------------ eval

@@ -36,6 +36,7 @@ from ..parallel.comm import DeviceComm, XgmiDeviceComm, all_reduce_grads_
 from ..utils import rng
 from ..utils.data import batch_offset
 from ..utils.schedule import learning_rate
+from .shuffle import make_shuffler
 
 # sync_schedule="auto": the single-communicator gradient-sync schedules
 # (buckets / serial / sharded / factors, defer (fp32), csrc/mnist_executor.h) are timed on real
@@ -73,6 +74,7 @@ class MnistEngineBase:
         self.drop_seed = cfg.seed
         self.drop_rank = 0 if cfg.same_seed_all_ranks else rank  # quirk Q14
         self.grad_sync = cfg.sync == "grad" and world > 1 and comm is not None
+        self.shuffler = None  # cfg.shuffle: the per-pass row order (runtime/shuffle.py)
 
     # views -----------------------------------------------------------------
     def param_views(self) -> Dict[str, torch.Tensor]:
@@ -115,12 +117,17 @@ class TorchMnistEngine(MnistEngineBase):
         self.train_x = torch.from_numpy(np.ascontiguousarray(train_x, np.float32)).to(device)
         self.train_y = torch.from_numpy(np.asarray(train_y).astype(np.int64)).to(device)
         self.last_loss = float("nan")
+        self.shuffler = make_shuffler(cfg, self.drop_rank, self.n_local, self.train_x, self.train_y)
+        if self.shuffler is not None:
+            self.train_x, self.train_y = self.shuffler.work_x, self.shuffler.work_y
 
     def dropout_mask(self, step: int, rows: int, salt: int = 0) -> torch.Tensor:
         key = rng.dropout_key(self.drop_seed, self.drop_rank, step, salt)
         return rng.keep_mask_torch(key, (rows, M.FC1_OUT), self.cfg.dropout_keep, self.device)
 
     def forward_backward(self, step: int):
+        if self.shuffler is not None:
+            self.shuffler.ensure(step)
         off = batch_offset(step, self.n_local, self.B)
         x = self.train_x[off:off + self.B]
         y = self.train_y[off:off + self.B]
@@ -226,6 +233,9 @@ class NativeMnistEngine(MnistEngineBase):
             ty = torch.cat([ty, torch.zeros(pad, dtype=ty.dtype)])
         self.train_x = tx.to(dev)
         self.train_y = ty.to(dev)
+        # (the working copy; the zero pad rows past n_local are never shuffled)
+        self.shuffler = make_shuffler(cfg, self.drop_rank, self.n_local, self.train_x, self.train_y,
+                                      native=C_)
         self.step_dev = torch.zeros(1, dtype=torch.int64, device=dev)
         self.lr_dev = torch.zeros(1, **f32)
         self.correct_dev = torch.zeros(1, dtype=torch.int32, device=dev)
@@ -514,6 +524,10 @@ class NativeMnistEngine(MnistEngineBase):
         steps = 0
         best = None
         self.exe.join(stream_handle())
+        if self.shuffler is not None:
+            # the trial steps read the order of the pass they start in (they are
+            # discarded; the working copy is what the step restored to reads)
+            self.shuffler.ensure(self.step)
         # the candidates' steps take the derived weights (Winograd transforms,
         # bf16 shadows) as current: derive them from the weights first
         self.exe.refresh_shadows(stream_handle())
@@ -666,6 +680,8 @@ class NativeMnistEngine(MnistEngineBase):
             return 0.0
         t_start = time.perf_counter()
         self.exe.join(stream_handle())
+        if self.shuffler is not None:
+            self.shuffler.ensure(self.step)
         self.exe.refresh_shadows(stream_handle())
         snap = (self.params.clone(), self.mom.clone(), self.step_dev.clone())
         t0 = time.perf_counter()
@@ -695,6 +711,21 @@ class NativeMnistEngine(MnistEngineBase):
         # writes do not).  Skipping the launch keeps it out of short timed runs.
         if self._derived_ver != self.params._version:
             self.exe.refresh_shadows(stream_handle())
+        if self.shuffler is None:
+            self._run_steps(k)
+        else:
+            # k is cut at the pass boundaries here, whatever the caller asked
+            # for; the pieces reuse the per-length graph cache
+            for p, m in self.shuffler.segments(self.step, k):
+                self.exe.join(stream_handle())  # no earlier step still in flight on the comm stream
+                self.shuffler.load(p)
+                self._run_steps(m)
+        self.exe.join(stream_handle())
+        self.step += k
+        self._derived_ver = self.params._version
+
+    def _run_steps(self, k: int) -> None:
+        """k steps on the shard as it stands: graph replays, else eager launches."""
         done = 0
         if self.use_graph:
             G = self.graph_steps
@@ -711,9 +742,6 @@ class NativeMnistEngine(MnistEngineBase):
                     done += rem
         for _ in range(k - done):  # eager (no graphs, or capture unavailable)
             self._launch_one()
-        self.exe.join(stream_handle())
-        self.step += k
-        self._derived_ver = self.params._version
 
     def capture(self, k: int) -> None:
         """Pre-captures the graphs `train(k)` will replay (outside timing)."""
@@ -727,6 +755,8 @@ class NativeMnistEngine(MnistEngineBase):
     def forward_backward_only(self) -> None:
         """Forward + backward into the flat grad buffer; no sync, no SGD, no
         step increment (used by the numerics tests)."""
+        if self.shuffler is not None:
+            self.shuffler.ensure(self.step)
         self.exe.forward_backward(stream_handle())
 
     def loss_value(self) -> float:

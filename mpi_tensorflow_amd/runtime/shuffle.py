@@ -1,0 +1,103 @@
+"""Per-pass shuffled training batches (--shuffle): the pass bookkeeping the
+engines share.
+
+The step kernels, the executors and the captured graphs read the batch of
+step s at `batch_offset(s)` of the engine's device-resident shard and know
+nothing of shuffling.  With shuffle on, the engine keeps a pristine copy of
+its shard beside that working copy, and the rows of pass p = `pass_of(s)`
+(the wrap period of the offset) are the pristine rows in the order
+`rng.shuffle_perm(rng.shuffle_key(seed, rank, p), n_local)`: loading a pass
+rewrites the working copy in place - one `shuffle_rows` launch on the compute
+stream (csrc/kernels/shuffle.hip; the permutation is computed in the kernel)
+or, on the PyTorch paths, an index with the host permutation.  The pointers
+never change, the order is a pure function of the step (a resumed run needs no
+extra state), and each rank permutes inside its own shard with its own key.
+"""
+
+from __future__ import annotations
+
+from typing import Iterator, Optional, Tuple
+
+import numpy as np
+import torch
+
+from ..utils import rng
+from ..utils.data import batch_offset, pass_of
+
+
+def batch_rows(seed: int, rank: int, step: int, n_local: int, batch: int) -> np.ndarray:
+    """Shard rows (pristine order) of the batch of step `step` with shuffle on."""
+    perm = rng.shuffle_perm(rng.shuffle_key(seed, rank, pass_of(step, n_local, batch)), n_local)
+    off = batch_offset(step, n_local, batch)
+    return perm[off:off + batch]
+
+
+class PassShuffler:
+    """Keeps `work_x` / `work_y` (the tensors the step reads; only their first
+    `n_local` rows are touched, rows past them are the any-batch-size pad) in
+    the order of one pass.  `native`: the extension module for the HIP path,
+    which rewrites the tensors passed in; None for the PyTorch path, which
+    leaves them untouched and hands out a working copy of its own
+    (`work_x` / `work_y`: the engine reads those instead)."""
+
+    def __init__(self, seed: int, rank: int, n_local: int, batch: int, work_x: torch.Tensor,
+                 work_y: torch.Tensor, native=None):
+        self.seed, self.rank, self.n, self.B = int(seed), int(rank), int(n_local), int(batch)
+        if native is not None:  # the executors hold the pointers of the working copy
+            self.work_x, self.work_y = work_x, work_y
+            self.src_x = work_x[:self.n].clone()
+            self.src_y = work_y[:self.n].clone()
+        else:  # a host tensor may alias the caller's array: it stays the pristine copy
+            self.src_x, self.src_y = work_x[:self.n], work_y[:self.n]
+            self.work_x, self.work_y = work_x.clone(), work_y.clone()
+        self.row_elems = int(np.prod(work_x.shape[1:]))
+        self._C = native
+        if native is not None and (work_x.dtype != torch.float32 or work_y.dtype != torch.int32):
+            raise TypeError("shuffle_rows moves fp32 rows and int32 labels")
+        self.loaded: Optional[int] = None  # the pass the working copy holds
+
+    def key(self, p: int) -> int:
+        return rng.shuffle_key(self.seed, self.rank, p)
+
+    def perm(self, p: int) -> np.ndarray:
+        return rng.shuffle_perm(self.key(p), self.n)
+
+    def load(self, p: int) -> None:
+        """Working copy := pristine rows in the order of pass p, on the
+        current stream (idempotent)."""
+        if p == self.loaded:
+            return
+        if self._C is not None:
+            from ..ops import ptr, stream_handle
+            self._C.ops.shuffle_rows(ptr(self.src_x), ptr(self.src_y), ptr(self.work_x),
+                                     ptr(self.work_y), self.n, self.row_elems, self.key(p),
+                                     stream_handle())
+        else:
+            idx = torch.from_numpy(self.perm(p)).to(self.work_x.device)
+            self.work_x[:self.n] = self.src_x[idx]
+            self.work_y[:self.n] = self.src_y[idx]
+        self.loaded = p
+
+    def ensure(self, step: int) -> None:
+        """The working copy holds the order the batch of `step` is read in."""
+        self.load(pass_of(step, self.n, self.B))
+
+    def segments(self, step: int, k: int) -> Iterator[Tuple[int, int]]:
+        """Cuts the k steps from `step` at the pass boundaries: (pass, steps)."""
+        while k > 0:
+            p = pass_of(step, self.n, self.B)
+            # first step of pass p + 1: the smallest s with s * B >= (p + 1) * (n - B)
+            nxt = -(-(p + 1) * (self.n - self.B) // self.B)
+            m = min(k, nxt - step)
+            yield p, m
+            step += m
+            k -= m
+
+
+def make_shuffler(cfg, rank: int, n_local: int, work_x: torch.Tensor, work_y: torch.Tensor,
+                  native=None) -> Optional[PassShuffler]:
+    """The engine's shuffler, or None (nothing allocated) with shuffle off.
+    `rank` is the rank of the engine's dropout stream (0 under quirk Q14)."""
+    if not getattr(cfg, "shuffle", False):
+        return None
+    return PassShuffler(cfg.seed, rank, n_local, cfg.batch_size, work_x, work_y, native)

@@ -39,6 +39,7 @@ from ..ops import functional as Fn
 from ..utils.data import batch_offset
 from ..utils.faults import maybe_fail
 from ..utils.profiling import SegmentTimer
+from .shuffle import batch_rows
 
 
 @dataclasses.dataclass
@@ -182,6 +183,11 @@ class Trainer:
         (/root/reference/mpipy.py:67): probabilities for the current training
         batch (rows at the step's batch offset, dropout on as in training)."""
         sh = self.shard
+        if self.cfg.shuffle:  # the rows the step reads: this pass's order of the shard
+            rank = 0 if self.cfg.same_seed_all_ranks else self.rank
+            rows = batch_rows(self.cfg.seed, rank, self.engine.step, sh.train_x.shape[0],
+                              self.cfg.batch_size)
+            return self.eval_prediction(sh.train_x[rows], dropout=True)
         off = batch_offset(self.engine.step, sh.train_x.shape[0], self.cfg.batch_size)
         return self.eval_prediction(sh.train_x[off:off + self.cfg.batch_size], dropout=True)
 

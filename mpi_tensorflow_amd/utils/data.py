@@ -89,6 +89,14 @@ def batch_offset(step: int, n_local: int, batch: int = C.BATCH_SIZE) -> int:
     return (step * batch) % (n_local - batch)
 
 
+def pass_of(step: int, n_local: int, batch: int = C.BATCH_SIZE) -> int:
+    """The pass step `step` belongs to: how often `batch_offset` has wrapped.
+    Within one pass the offsets rise by `batch`, so no row repeats."""
+    if n_local <= batch:
+        raise ValueError(f"local shard ({n_local} rows) must exceed the batch ({batch})")
+    return (step * batch) // (n_local - batch)
+
+
 def num_syncs(steps: int, every: int = C.SYNC_EVERY) -> int:
     """How many periodic syncs a run performs (step>0 and step%every==0)."""
     return max(0, (steps - 1) // every)
