@@ -79,6 +79,42 @@ COMMS = ("auto", "rccl", "shm", "xgmi", "torch")
 # LeNet-5's sync over the xGMI communicator (TrainConfig.xgmi_mode)
 XGMI_MODES = ("two-phase", "push", "pull")
 DTYPES = ("fp32", "bf16")
+# --augment: what is shifted in from outside the image unless the spec says
+# fill:V.  MNIST: the normalised raw 0 pixel, (0 - 127.5) / 255; the others:
+# zero-padding of a centred image
+AUGMENT_FILL = {"mnist_cnn": -0.5, "lenet5": 0.0, "resnet18": 0.0}
+
+
+def parse_augment(spec: str, model: str = "mnist_cnn"):
+    """`shift:K` (K >= 1), `flip` and optionally `fill:V`, comma separated, in
+    any order, each at most once -> (K, flip, fill); K = 0 without a shift."""
+    if not isinstance(spec, str) or not spec.strip():
+        raise ValueError("empty augment spec; expected e.g. 'shift:2', 'shift:4,flip', 'flip'")
+    seen = {}
+    for item in spec.split(","):
+        name, sep, val = item.strip().partition(":")
+        if name in seen:
+            raise ValueError(f"augment spec {spec!r} names {name!r} twice")
+        try:
+            if name == "shift" and sep:
+                seen[name] = int(val)
+            elif name == "fill" and sep:
+                seen[name] = float(val)
+                if seen[name] != seen[name] or abs(seen[name]) == float("inf"):
+                    raise ValueError
+            elif name == "flip" and not sep:
+                seen[name] = True
+            else:
+                raise ValueError
+        except ValueError:
+            raise ValueError(f"bad item {item!r} in augment spec {spec!r}; expected shift:K, "
+                             f"flip or fill:V") from None
+    K = seen.get("shift", 0)
+    if "shift" in seen and K < 1:
+        raise ValueError(f"augment shift must be at least 1, got {K}")
+    if "shift" not in seen and "flip" not in seen:
+        raise ValueError(f"augment spec {spec!r} asks for neither a shift nor a flip")
+    return K, "flip" in seen, float(seen.get("fill", AUGMENT_FILL.get(model, 0.0)))
 
 
 @dataclasses.dataclass
@@ -138,6 +174,10 @@ class TrainConfig:
     # a new row order for every pass over the local shard (runtime/shuffle.py);
     # off = the reference's file order (mpipy.py:80), the same batches every pass
     shuffle: bool = False
+    # per-pass random shift / horizontal flip of the training images, redrawn
+    # for every row and pass on the device (parse_augment, runtime/shuffle.py);
+    # None = every pass shows the same pixels
+    augment: Optional[str] = None
     # learning rate / optimiser
     base_lr: float = BASE_LR
     lr_decay: float = LR_DECAY
@@ -196,6 +236,8 @@ class TrainConfig:
             raise ValueError("sync_every must be > 0 and eval_every >= 0")
         if not 0.0 < self.dropout_keep <= 1.0:
             raise ValueError("dropout_keep must be in (0, 1]")
+        if self.augment is not None:
+            parse_augment(self.augment, self.model)
         return self
 
     # quirk accessors ------------------------------------------------------
@@ -267,6 +309,10 @@ def build_arg_parser(prog: str = "mpipy.py") -> argparse.ArgumentParser:
     p.add_argument("--shuffle", action="store_true",
                    help="permute each rank's shard anew for every pass (on the device, a pure "
                         "function of seed, rank and pass; the reference reads in file order)")
+    p.add_argument("--augment", default=d.augment, metavar="SPEC",
+                   help="random shift and / or horizontal flip of every training image, redrawn "
+                        "each pass on the device: shift:K[,flip][,fill:V] or flip (fill: the value "
+                        "shifted in, default -0.5 for mnist_cnn, 0 otherwise)")
     p.add_argument("--base-lr", type=float, default=d.base_lr)
     p.add_argument("--lr-decay", type=float, default=d.lr_decay)
     p.add_argument("--momentum", type=float, default=d.momentum)

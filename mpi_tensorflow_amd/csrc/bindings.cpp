@@ -11,6 +11,7 @@
 #include <pybind11/stl.h>
 
 #include "idx_loader.h"
+#include "kernels/augment.h"
 #include "kernels/mnist.h"
 #include "kernels/mnist_bf16.h"
 #include "kernels/ops_generic.h"
@@ -741,6 +742,16 @@ PYBIND11_MODULE(_C, m) {
     shuffle::shuffle_perm(P<int>(out), n, key, S(st));
     check_launch();
   });
+  // ... and the per-pass shift / flip augmentation fused with it (kernels/augment.h)
+  g.def("augment_rows", [](uintptr_t src_x, uintptr_t src_y, uintptr_t dst_x, uintptr_t dst_y,
+                           long long n, int H, int W, int C, bool use_perm, uint32_t perm_key,
+                           uint32_t aug_key, int K, bool flip, float fill, uintptr_t st) {
+    augment::augment_rows(P<const float>(src_x), P<const int>(src_y), P<float>(dst_x), P<int>(dst_y),
+                          n, H, W, C, use_perm, perm_key, aug_key, K, flip, fill, S(st));
+    check_launch();
+  }, py::arg("src_x"), py::arg("src_y"), py::arg("dst_x"), py::arg("dst_y"), py::arg("n"),
+     py::arg("H"), py::arg("W"), py::arg("C"), py::arg("use_perm"), py::arg("perm_key"),
+     py::arg("aug_key"), py::arg("K"), py::arg("flip"), py::arg("fill"), py::arg("st"));
 
   // ------------------------------------------------------------ executor
   py::class_<MnistPtrs>(m, "MnistPtrs")

@@ -136,12 +136,14 @@ class GenericEngine:
             if self.wcache.njobs == 0:  # (LeNet-5 etc.: nothing to keep)
                 self.wcache = None
             self._wfresh = False  # the copies match the fp32 weights
-        # cfg.shuffle: the per-pass row order of train_x / train_y (runtime/shuffle.py;
-        # keyed by the rank of the dropout stream, Q14): the HIP gather on the
-        # native path, the host permutation on the PyTorch paths
+        # cfg.shuffle / cfg.augment: the per-pass row order and shift / flip of train_x /
+        # train_y (runtime/shuffle.py; keyed by the rank of the dropout stream, Q14): the
+        # HIP gather on the native path, the host permutation and transform on the
+        # PyTorch paths
         self.shuffler = make_shuffler(cfg, 0 if cfg.same_seed_all_ranks else rank, self.n_local,
                                       self.train_x, self.train_y,
-                                      native=self._C if self.on_gpu else None)
+                                      native=self._C if self.on_gpu else None,
+                                      image_shape=tuple(self.train_x.shape[1:]))
         if self.shuffler is not None:
             self.train_x, self.train_y = self.shuffler.work_x, self.shuffler.work_y
 

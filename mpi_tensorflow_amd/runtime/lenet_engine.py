@@ -80,10 +80,12 @@ class NativeLenetEngine:
             self.grad_sync = True
         C_ = native()
         self._C = C_
-        # cfg.shuffle: the per-pass row order of the working copy above
-        # (runtime/shuffle.py; keyed by the rank of the dropout stream, Q14)
+        # cfg.shuffle / cfg.augment: the per-pass row order and shift / flip of the
+        # working copy above (runtime/shuffle.py; keyed by the rank of the dropout
+        # stream, Q14)
         self.shuffler = make_shuffler(cfg, 0 if cfg.same_seed_all_ranks else rank, self.n_local,
-                                      self.train_x, self.train_y, native=C_)
+                                      self.train_x, self.train_y, native=C_,
+                                      image_shape=(32, 32, 3))
         na, nd, nc = C_.lenet_buffer_floats(self.B)
         self.acts = torch.zeros(na, device=dev)
         self.deltas = torch.zeros(nd, device=dev)

@@ -74,7 +74,7 @@ class MnistEngineBase:
         self.drop_seed = cfg.seed
         self.drop_rank = 0 if cfg.same_seed_all_ranks else rank  # quirk Q14
         self.grad_sync = cfg.sync == "grad" and world > 1 and comm is not None
-        self.shuffler = None  # cfg.shuffle: the per-pass row order (runtime/shuffle.py)
+        self.shuffler = None  # cfg.shuffle / cfg.augment: the per-pass rows (runtime/shuffle.py)
 
     # views -----------------------------------------------------------------
     def param_views(self) -> Dict[str, torch.Tensor]:
@@ -117,7 +117,8 @@ class TorchMnistEngine(MnistEngineBase):
         self.train_x = torch.from_numpy(np.ascontiguousarray(train_x, np.float32)).to(device)
         self.train_y = torch.from_numpy(np.asarray(train_y).astype(np.int64)).to(device)
         self.last_loss = float("nan")
-        self.shuffler = make_shuffler(cfg, self.drop_rank, self.n_local, self.train_x, self.train_y)
+        self.shuffler = make_shuffler(cfg, self.drop_rank, self.n_local, self.train_x, self.train_y,
+                                      image_shape=(28, 28, 1))
         if self.shuffler is not None:
             self.train_x, self.train_y = self.shuffler.work_x, self.shuffler.work_y
 
@@ -235,7 +236,7 @@ class NativeMnistEngine(MnistEngineBase):
         self.train_y = ty.to(dev)
         # (the working copy; the zero pad rows past n_local are never shuffled)
         self.shuffler = make_shuffler(cfg, self.drop_rank, self.n_local, self.train_x, self.train_y,
-                                      native=C_)
+                                      native=C_, image_shape=(28, 28, 1))
         self.step_dev = torch.zeros(1, dtype=torch.int64, device=dev)
         self.lr_dev = torch.zeros(1, **f32)
         self.correct_dev = torch.zeros(1, dtype=torch.int32, device=dev)

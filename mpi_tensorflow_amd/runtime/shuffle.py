@@ -1,5 +1,5 @@
-"""Per-pass shuffled training batches (--shuffle): the pass bookkeeping the
-engines share.
+"""Per-pass shuffled (--shuffle) and augmented (--augment) training batches:
+the pass bookkeeping the engines share.
 
 The step kernels, the executors and the captured graphs read the batch of
 step s at `batch_offset(s)` of the engine's device-resident shard and know
@@ -12,6 +12,14 @@ stream (csrc/kernels/shuffle.hip; the permutation is computed in the kernel)
 or, on the PyTorch paths, an index with the host permutation.  The pointers
 never change, the order is a pure function of the step (a resumed run needs no
 extra state), and each rank permutes inside its own shard with its own key.
+
+With augment on, the same load also shifts and flips every image
+(`rng.augment_params` / `rng.augment_np` are the definition): the draw of a row
+is a pure function of (seed, rank, pass, pristine row index), so it means the
+same with and without shuffle, pass 0 included.  On the native path the load
+stays one launch (`augment_rows`, csrc/kernels/augment.hip: the gather and the
+transform in one pass over the shard); with augment alone the order is the
+file order.
 """
 
 from __future__ import annotations
@@ -38,11 +46,26 @@ class PassShuffler:
     the order of one pass.  `native`: the extension module for the HIP path,
     which rewrites the tensors passed in; None for the PyTorch path, which
     leaves them untouched and hands out a working copy of its own
-    (`work_x` / `work_y`: the engine reads those instead)."""
+    (`work_x` / `work_y`: the engine reads those instead).
+
+    `augment`: None or (K, flip, fill, (H, W, C)), the per-pass shift / flip of
+    the NHWC images; `shuffle=False` keeps the file order (augment only)."""
 
     def __init__(self, seed: int, rank: int, n_local: int, batch: int, work_x: torch.Tensor,
-                 work_y: torch.Tensor, native=None):
+                 work_y: torch.Tensor, native=None, augment=None, shuffle: bool = True):
         self.seed, self.rank, self.n, self.B = int(seed), int(rank), int(n_local), int(batch)
+        self.shuffle = bool(shuffle)
+        self.augment = None
+        if augment is not None:
+            K, flip, fill, (H, W, C) = augment
+            K, H, W, C = int(K), int(H), int(W), int(C)
+            if K < 0 or K >= min(H, W):
+                raise ValueError(f"augment shift {K} must be below min(H, W) = {min(H, W)}")
+            if tuple(work_x.shape[1:]) != (H, W, C):
+                raise ValueError(f"augment: rows of shape {tuple(work_x.shape[1:])}, images "
+                                 f"{(H, W, C)}")
+            if K > 0 or flip:
+                self.augment = (K, bool(flip), float(fill), (H, W, C))
         if native is not None:  # the executors hold the pointers of the working copy
             self.work_x, self.work_y = work_x, work_y
             self.src_x = work_x[:self.n].clone()
@@ -60,22 +83,41 @@ class PassShuffler:
         return rng.shuffle_key(self.seed, self.rank, p)
 
     def perm(self, p: int) -> np.ndarray:
-        return rng.shuffle_perm(self.key(p), self.n)
+        """Pristine row of every working row in pass p."""
+        return rng.shuffle_perm(self.key(p), self.n) if self.shuffle else np.arange(self.n)
+
+    def augment_key(self, p: int) -> int:
+        return rng.augment_key(self.seed, self.rank, p)
 
     def load(self, p: int) -> None:
-        """Working copy := pristine rows in the order of pass p, on the
-        current stream (idempotent)."""
+        """Working copy := pristine rows in the order, and with the draws, of
+        pass p, on the current stream (idempotent)."""
         if p == self.loaded:
             return
         if self._C is not None:
             from ..ops import ptr, stream_handle
-            self._C.ops.shuffle_rows(ptr(self.src_x), ptr(self.src_y), ptr(self.work_x),
-                                     ptr(self.work_y), self.n, self.row_elems, self.key(p),
-                                     stream_handle())
+            if self.augment is None:
+                self._C.ops.shuffle_rows(ptr(self.src_x), ptr(self.src_y), ptr(self.work_x),
+                                         ptr(self.work_y), self.n, self.row_elems, self.key(p),
+                                         stream_handle())
+            else:
+                K, flip, fill, (H, W, C) = self.augment
+                self._C.ops.augment_rows(ptr(self.src_x), ptr(self.src_y), ptr(self.work_x),
+                                         ptr(self.work_y), self.n, H, W, C, self.shuffle,
+                                         self.key(p) if self.shuffle else 0, self.augment_key(p),
+                                         K, flip, fill, stream_handle())
         else:
-            idx = torch.from_numpy(self.perm(p)).to(self.work_x.device)
-            self.work_x[:self.n] = self.src_x[idx]
-            self.work_y[:self.n] = self.src_y[idx]
+            rows = self.perm(p)
+            x, y = self.src_x, self.src_y
+            if self.shuffle:
+                idx = torch.from_numpy(rows).to(self.work_x.device)
+                x, y = x[idx], y[idx]
+            if self.augment is not None:
+                K, flip, fill, _ = self.augment
+                x = rng.augment_torch(x, *rng.augment_params(self.augment_key(p), rows, K, flip),
+                                      fill)
+            self.work_x[:self.n] = x
+            self.work_y[:self.n] = y
         self.loaded = p
 
     def ensure(self, step: int) -> None:
@@ -95,9 +137,19 @@ class PassShuffler:
 
 
 def make_shuffler(cfg, rank: int, n_local: int, work_x: torch.Tensor, work_y: torch.Tensor,
-                  native=None) -> Optional[PassShuffler]:
-    """The engine's shuffler, or None (nothing allocated) with shuffle off.
-    `rank` is the rank of the engine's dropout stream (0 under quirk Q14)."""
-    if not getattr(cfg, "shuffle", False):
+                  native=None, image_shape=None) -> Optional[PassShuffler]:
+    """The engine's shuffler, or None (nothing allocated) with shuffle and
+    augment off.  `rank` is the rank of the engine's dropout stream (0 under
+    quirk Q14); `image_shape`: (H, W, C) of a row, which augment needs."""
+    shuffle = bool(getattr(cfg, "shuffle", False))
+    spec = getattr(cfg, "augment", None)
+    if not shuffle and spec is None:
         return None
-    return PassShuffler(cfg.seed, rank, n_local, cfg.batch_size, work_x, work_y, native)
+    augment = None
+    if spec is not None:
+        from ..config import parse_augment
+        if image_shape is None:
+            raise ValueError("augment needs the image shape of the shard's rows")
+        augment = parse_augment(spec, cfg.model) + (tuple(int(v) for v in image_shape),)
+    return PassShuffler(cfg.seed, rank, n_local, cfg.batch_size, work_x, work_y, native,
+                        augment=augment, shuffle=shuffle)

@@ -36,7 +36,8 @@ from ..utils.data import (data_exist_here, load_mnist_shard, local_train_rows, m
                           steps_per_run, synthetic_image_shard)
 from ..utils.logging import MetricsWriter, emit, progress_line, start_line
 from ..ops import functional as Fn
-from ..utils.data import batch_offset
+from ..utils import rng
+from ..utils.data import batch_offset, pass_of
 from ..utils.faults import maybe_fail
 from ..utils.profiling import SegmentTimer
 from .shuffle import batch_rows
@@ -182,14 +183,20 @@ class Trainer:
         """`train_prediction = softmax(logits)` of the reference's training graph
         (/root/reference/mpipy.py:67): probabilities for the current training
         batch (rows at the step's batch offset, dropout on as in training)."""
-        sh = self.shard
-        if self.cfg.shuffle:  # the rows the step reads: this pass's order of the shard
-            rank = 0 if self.cfg.same_seed_all_ranks else self.rank
-            rows = batch_rows(self.cfg.seed, rank, self.engine.step, sh.train_x.shape[0],
-                              self.cfg.batch_size)
-            return self.eval_prediction(sh.train_x[rows], dropout=True)
-        off = batch_offset(self.engine.step, sh.train_x.shape[0], self.cfg.batch_size)
-        return self.eval_prediction(sh.train_x[off:off + self.cfg.batch_size], dropout=True)
+        sh, cfg, step = self.shard, self.cfg, self.engine.step
+        n, B = sh.train_x.shape[0], cfg.batch_size
+        rank = 0 if cfg.same_seed_all_ranks else self.rank
+        if cfg.shuffle:  # the rows the step reads: this pass's order of the shard
+            rows = batch_rows(cfg.seed, rank, step, n, B)
+        else:
+            off = batch_offset(step, n, B)
+            rows = np.arange(off, off + B)
+        x = sh.train_x[rows]
+        if cfg.augment is not None:  # ... with this pass's shift / flip of each of them
+            K, flip, fill = C.parse_augment(cfg.augment, cfg.model)
+            key = rng.augment_key(cfg.seed, rank, pass_of(step, n, B))
+            x = rng.augment_np(x, *rng.augment_params(key, rows, K, flip), fill)
+        return self.eval_prediction(x, dropout=True)
 
     def check_replicas(self, step: int, averaged: bool = False) -> None:
         """All ranks must hold bit-identical weights under per-step gradient

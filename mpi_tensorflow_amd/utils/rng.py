@@ -26,6 +26,7 @@ GOLDEN = 0x9E3779B9
 STEP_MUL = 0x85EBCA6B
 EVAL_SALT = 0x5BD1E995  # separates the eval-time (quirk Q8) stream
 SHUFFLE_SALT = 0x2545F491  # ... and the per-pass row order (--shuffle)
+AUGMENT_SALT = 0x68E31DA4  # ... and the per-pass shift / flip draws (--augment)
 
 
 def _mix_np(x: np.ndarray) -> np.ndarray:
@@ -77,6 +78,70 @@ def shuffle_perm(key: int, n: int) -> np.ndarray:
         if out.size == 0:
             return x.astype(np.int64)
         x[out] = _feistel_np(x[out], h, rk)
+
+
+def augment_key(seed: int, rank: int, pass_: int) -> int:
+    """Key of the augmentation draws of training pass `pass_` (--augment);
+    `rank` as in `shuffle_key`."""
+    return dropout_key(seed, rank, pass_, AUGMENT_SALT)
+
+
+def augment_params(key: int, rows, K: int, flip: bool):
+    """(dy, dx, flipped) of the pristine shard rows `rows` under `key`: a pure
+    function of (key, row), so the order and the grouping of `rows` do not
+    matter.  dy, dx int64 in [-K, K] (the modulo bias is below (2K+1) / 2^32),
+    flipped bool (all False without `flip`).  The device side is
+    `csrc/kernels/augment.hip`.
+
+        h0 = mix(key ^ row), h1 = mix(h0 + GOLDEN), h2 = mix(h1 + GOLDEN)
+        dy = h0 % (2K+1) - K, dx = h1 % (2K+1) - K, flipped = h2 >> 31
+    """
+    s = np.asarray(rows).astype(np.uint64)
+    h0 = _mix_np(s ^ np.uint64(key))
+    h1 = _mix_np(h0 + np.uint64(GOLDEN))
+    h2 = _mix_np(h1 + np.uint64(GOLDEN))
+    span = np.uint64(2 * K + 1)
+    dy = (h0 % span).astype(np.int64) - K
+    dx = (h1 % span).astype(np.int64) - K
+    fl = (h2 >> np.uint64(31)).astype(bool) if flip else np.zeros(s.shape, bool)
+    return dy, dx, fl
+
+
+def _augment_index(xp, n, H, W, dy, dx, fl):
+    """Source line / column of every output line / column, [n, H] and [n, W]
+    (`xp`: numpy or torch, whose arange / where agree here)."""
+    ys = xp.arange(H)[None, :] + dy[:, None]
+    cols = xp.arange(W)[None, :]
+    xs = xp.where(fl[:, None], W - 1 - cols, cols) + dx[:, None]
+    return ys, xs
+
+
+def augment_np(x_nhwc: np.ndarray, dy, dx, flip, fill: float) -> np.ndarray:
+    """out[i, y, x, c] = x[i, y + dy[i], xs + dx[i], c] with xs = W - 1 - x where
+    flip[i], else x; `fill` where that pixel lies outside the image."""
+    x = np.asarray(x_nhwc)
+    n, H, W, _ = x.shape
+    ys, xs = _augment_index(np, n, H, W, np.asarray(dy), np.asarray(dx), np.asarray(flip, bool))
+    inside = (((ys >= 0) & (ys < H))[:, :, None] & ((xs >= 0) & (xs < W))[:, None, :])[..., None]
+    got = x[np.arange(n)[:, None, None], ys.clip(0, H - 1)[:, :, None], xs.clip(0, W - 1)[:, None, :]]
+    return np.where(inside, got, x.dtype.type(fill))
+
+
+def augment_torch(x_nhwc, dy, dx, flip, fill: float):
+    """`augment_np` on a torch tensor, on its device (dy, dx, flip: numpy)."""
+    import torch
+
+    x = x_nhwc
+    n, H, W, _ = x.shape
+    dev = x.device
+    ys, xs = _augment_index(torch, n, H, W, torch.from_numpy(np.asarray(dy, np.int64)),
+                            torch.from_numpy(np.asarray(dx, np.int64)),
+                            torch.from_numpy(np.asarray(flip, bool)))
+    ys, xs = ys.to(dev), xs.to(dev)
+    inside = (((ys >= 0) & (ys < H))[:, :, None] & ((xs >= 0) & (xs < W))[:, None, :])[..., None]
+    got = x[torch.arange(n, device=dev)[:, None, None], ys.clamp(0, H - 1)[:, :, None],
+            xs.clamp(0, W - 1)[:, None, :]]
+    return torch.where(inside, got, torch.full((), fill, dtype=x.dtype, device=dev))
 
 
 def keep_mask_np(key: int, n: int, keep_prob: float) -> np.ndarray:
