@@ -196,6 +196,13 @@ class TrainConfig:
     ckpt_every: int = 0
     resume: Optional[str] = None
     metrics_jsonl: Optional[str] = None
+    # at every logged eval event and at the end: held-out loss, top-3 error,
+    # confusion matrix of the test split and the validation split's error /
+    # loss, summed over the ranks (utils/metrics.py, Trainer.evaluate_metrics)
+    eval_metrics: bool = False
+    # checkpoint written whenever the global validation error improves
+    # (strictly); implies eval_metrics
+    ckpt_best: Optional[str] = None
     quiet: bool = False
     # robustness: process-group / collective timeout (a dead rank turns into
     # an error instead of a hang) and a cross-replica consistency probe at
@@ -238,6 +245,13 @@ class TrainConfig:
             raise ValueError("dropout_keep must be in (0, 1]")
         if self.augment is not None:
             parse_augment(self.augment, self.model)
+        if self.ckpt_best:
+            if self.model != "mnist_cnn":
+                raise ValueError(f"--ckpt-best selects on the validation split, and the "
+                                 f"{self.model} shards have no validation rows")
+            if self.effective_eval_every() == 0:
+                raise ValueError("--ckpt-best needs periodic evaluation (--eval-every > 0)")
+            self.eval_metrics = True
         return self
 
     # quirk accessors ------------------------------------------------------
@@ -328,6 +342,13 @@ def build_arg_parser(prog: str = "mpipy.py") -> argparse.ArgumentParser:
     p.add_argument("--ckpt-every", type=int, default=0)
     p.add_argument("--resume", default=None)
     p.add_argument("--metrics-jsonl", default=None)
+    p.add_argument("--eval-metrics", action="store_true",
+                   help="at every logged eval event and at the end: test loss, top-3 error and "
+                        "confusion matrix, validation error and loss, summed over the ranks "
+                        "(one extra log line on rank 0, extra keys in --metrics-jsonl)")
+    p.add_argument("--ckpt-best", default=None, metavar="PATH",
+                   help="write the checkpoint there whenever the global validation error "
+                        "improves (implies --eval-metrics; mnist_cnn, --eval-every > 0)")
     p.add_argument("--quiet", action="store_true")
     p.add_argument("--collective-timeout-s", type=float, default=d.collective_timeout_s,
                    help="process-group / collective timeout (seconds)")

@@ -574,6 +574,15 @@ PYBIND11_MODULE(_C, m) {
     gops::softmax_rows(P<const float>(x), P<float>(y), M, N, S(st));
     check_launch();
   });
+  g.def("eval_metrics_ws_doubles", &gops::eval_metrics_ws_doubles);
+  g.def("eval_metrics", [](uintptr_t logits, uintptr_t labels, int n, int C, uintptr_t conf,
+                           uintptr_t rank_hist, uintptr_t loss_sum, uintptr_t ignored,
+                           uintptr_t ws, uintptr_t loss_rows, uintptr_t st) {
+    gops::eval_metrics(P<const float>(logits), P<const int>(labels), n, C, P<int>(conf),
+                       P<int>(rank_hist), P<double>(loss_sum), P<int>(ignored), P<double>(ws),
+                       P<float>(loss_rows), S(st));
+    check_launch();
+  });
   g.def("wcvt_blocks", &gops::wcvt_blocks);
   g.def("sgd_wcvt", [](uintptr_t w, uintptr_t gr, uintptr_t mom, float momentum, float gscale,
                        float l2, uintptr_t lr, uintptr_t step, uintptr_t jobs, int njobs,

@@ -262,6 +262,15 @@ void xent(const float* logits, const int* labels, int B, int C, float* loss_rows
           int* correct, hipStream_t st);
 void relu_bwd(const float* dy, const float* y, float* dx, long long n, hipStream_t st);
 void softmax_rows(const float* x, float* y, int M, int N, hipStream_t st);
+// eval_metrics.hip: evaluation metrics of n rows of C <= 64 logits, ADDED to
+// conf [C][C] (label, prediction = lowest index among the maximal logits),
+// rank_hist [C] (classes ahead of the label: greater, or equal with a lower
+// index), loss_sum (fp64 sum of logsumexp(row) - row[label], fp32 per row) and
+// ignored (labels outside [0, C); they count nowhere else).  ws:
+// eval_metrics_ws_doubles() doubles; loss_rows (optional, [n]): each row's loss
+int eval_metrics_ws_doubles();
+void eval_metrics(const float* logits, const int* labels, int n, int C, int* conf, int* rank_hist,
+                  double* loss_sum, int* ignored, double* ws, float* loss_rows, hipStream_t st);
 // stem im2col route: HWIO weight -> bf16 [K][kp] (im2col k order), and the
 // [kp][K] filter gradient back to HWIO
 void stem_weight_bf16(const float* w, int R, int sc, int seg, int kp, int K, void* out,

@@ -807,6 +807,112 @@ def softmax(logits: torch.Tensor) -> torch.Tensor:
     return y
 
 
+# ------------------------------------------------------- evaluation metrics --
+class EvalMetricsOut:
+    """The accumulators of one evaluation, owned by the caller: pass it as
+    `out` to every chunk's eval_metrics call, then read `result()` once.
+
+    On the GPU they are one int32 buffer of C * C + C + 4 words - confusion
+    [C, C], rank histogram [C], the fp64 loss sum (2 words, 8-byte aligned: C *
+    C + C is even), ignored rows, one pad word - plus the kernel's workspace
+    of per-block loss partials; result() is the evaluation's only D2H copy.
+    On the oracle path they are a host EvalMetrics."""
+
+    def __init__(self, classes: int, device: torch.device, oracle: bool = False):
+        from ..utils.metrics import EvalMetrics
+
+        if not 1 <= classes <= 64:
+            raise ValueError(f"eval_metrics takes 1 to 64 classes, got {classes}")
+        self.classes = int(classes)
+        self.device = torch.device(device)
+        self.native = self.device.type == "cuda" and not oracle
+        if self.native:
+            c = self.classes
+            self.buf = torch.zeros(c * c + c + 4, dtype=torch.int32, device=self.device)
+            self.ws = torch.empty(native().ops.eval_metrics_ws_doubles(), dtype=torch.float64,
+                                  device=self.device)
+        else:
+            self.acc = EvalMetrics.zeros(self.classes)
+
+    def zero_(self) -> "EvalMetricsOut":
+        from ..utils.metrics import EvalMetrics
+
+        if self.native:
+            self.buf.zero_()
+        else:
+            self.acc = EvalMetrics.zeros(self.classes)
+        return self
+
+    def result(self):
+        from ..utils.metrics import EvalMetrics
+
+        if not self.native:
+            return self.acc
+        c = self.classes
+        h = self.buf.cpu().numpy()
+        conf = h[:c * c].reshape(c, c).astype("int64")
+        loss = float(h[c * c + c:c * c + c + 2].view("float64")[0])
+        return EvalMetrics(int(conf.sum()), int(h[c * c + c + 2]), loss, conf,
+                           h[c * c:c * c + c].astype("int64"))
+
+
+def _eval_metrics_oracle(logits: torch.Tensor, labels: torch.Tensor):
+    """fp64 torch implementation of the definitions in utils/metrics.py."""
+    from ..utils.metrics import EvalMetrics
+
+    x = logits.detach().to("cpu", torch.float64)
+    t = labels.detach().to("cpu", torch.int64)
+    c = x.shape[1]
+    valid = (t >= 0) & (t < c)
+    ignored = int((~valid).sum())
+    x, t = x[valid], t[valid]
+    idx = torch.arange(c, dtype=torch.int64)
+    top = x == x.max(dim=1, keepdim=True).values
+    pred = torch.where(top, idx, torch.full_like(idx, c)).min(dim=1).values.clamp_(max=c - 1)
+    xl = x.gather(1, t[:, None])
+    rank = (x > xl).sum(dim=1) + ((x == xl) & (idx[None, :] < t[:, None])).sum(dim=1)
+    loss = torch.logsumexp(x, dim=1) - xl[:, 0]
+    conf = torch.bincount(t * c + pred, minlength=c * c).reshape(c, c)
+    return EvalMetrics(int(x.shape[0]), ignored, float(loss.sum()), conf.numpy(),
+                       torch.bincount(rank, minlength=c).numpy())
+
+
+def eval_metrics(logits: torch.Tensor, labels: torch.Tensor, out: Optional[EvalMetricsOut] = None,
+                 loss_rows: Optional[torch.Tensor] = None):
+    """Evaluation metrics of [n, C] logits (C <= 64) against [n] labels:
+    confusion matrix, histogram of the label's rank, summed cross-entropy,
+    ignored rows (utils/metrics.py has the definitions).  Native kernel on the
+    GPU (eval_metrics.hip), fp64 torch on the CPU oracle path.
+
+    Without `out`: returns the EvalMetrics of these rows.  With `out`: the rows
+    are added to the caller's accumulators, nothing is copied back or waited
+    for, `out` is returned, and `out.result()` gives the total.  loss_rows
+    (GPU, optional fp32 [n]): also receives each row's loss (0 for an ignored
+    row)."""
+    n, c = int(logits.shape[0]), int(logits.shape[1])
+    if labels.shape[0] != n:
+        raise ValueError(f"{n} rows of logits but {labels.shape[0]} labels")
+    oracle = not logits.is_cuda or _ORACLE
+    own = out is None
+    if own:
+        out = EvalMetricsOut(c, logits.device, oracle=oracle)
+    elif out.classes != c or out.native == oracle:
+        raise ValueError("`out` was made for another class count or another path")
+    if oracle:
+        out.acc = out.acc + _eval_metrics_oracle(logits, labels)
+    elif n > 0:
+        x = logits.detach().float().contiguous()
+        t = labels.to(device=x.device, dtype=torch.int32).contiguous()
+        if loss_rows is not None and (loss_rows.dtype != torch.float32 or loss_rows.numel() < n
+                                      or not loss_rows.is_contiguous()):
+            raise ValueError("loss_rows must be a contiguous fp32 tensor of at least n elements")
+        b, w = ptr(out.buf), 4
+        native().ops.eval_metrics(ptr(x), ptr(t), n, c, b, b + w * c * c, b + w * (c * c + c),
+                                  b + w * (c * c + c + 2), ptr(out.ws), ptr(loss_rows),
+                                  stream_handle())
+    return out.result() if own else out
+
+
 # ---------------------------------------------------------------- pooling --
 class _MaxPoolFn(torch.autograd.Function):
     @staticmethod

@@ -143,6 +143,23 @@ def allreduce_sum_host(x: float) -> float:
     return float(x)
 
 
+def allreduce_sum_host_array(a):
+    """Element-wise sum of a host array over the ranks (gloo), in float64 for
+    a floating array and int64 for an integer one; the array's own values (as
+    that dtype) at world 1."""
+    import numpy as np
+
+    a = np.asarray(a)
+    if a.dtype.kind not in "fiub":
+        raise TypeError(f"cannot all-reduce an array of dtype {a.dtype}")
+    a = np.ascontiguousarray(a, np.float64 if a.dtype.kind == "f" else np.int64)
+    if dist.is_available() and dist.is_initialized() and dist.get_world_size() > 1:
+        t = torch.from_numpy(a.copy())
+        dist.all_reduce(t, op=dist.ReduceOp.SUM)
+        return t.numpy()
+    return a
+
+
 def shutdown() -> None:
     if dist.is_available() and dist.is_initialized():
         dist.destroy_process_group()

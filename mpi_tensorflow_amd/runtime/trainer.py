@@ -38,6 +38,8 @@ from ..utils.logging import MetricsWriter, emit, progress_line, start_line
 from ..ops import functional as Fn
 from ..utils import rng
 from ..utils.data import batch_offset, pass_of
+from ..utils.devcache import DeviceArrayCache
+from ..utils.metrics import EvalMetrics
 from ..utils.faults import maybe_fail
 from ..utils.profiling import SegmentTimer
 from .shuffle import batch_rows
@@ -64,9 +66,20 @@ class RunSummary:
     synthetic: bool
     sync_schedule: str = "n/a"
     xgmi_gate: str = "n/a"
+    # --eval-metrics only (global, summed over the ranks); left out of
+    # as_dict() while unset, so a run without the flag reports what it always did
+    final_test_loss: Optional[float] = None
+    final_val_error: Optional[float] = None
+    final_val_loss: Optional[float] = None
+
+    _OPTIONAL = ("final_test_loss", "final_val_error", "final_val_loss")
 
     def as_dict(self) -> Dict:
-        return dataclasses.asdict(self)
+        d = dataclasses.asdict(self)
+        for k in self._OPTIONAL:
+            if d[k] is None:
+                del d[k]
+        return d
 
 
 class Trainer:
@@ -99,6 +112,16 @@ class Trainer:
                                     expect={"model": cfg.model, "world": self.world})
             self.engine.set_step(step)
         self.metrics = MetricsWriter(cfg.metrics_jsonl, self.rank)
+        # the native MNIST engine evaluates device arrays: the test and the
+        # validation split are uploaded at their first evaluation and stay
+        # resident (the other GPU engines keep their own copy, utils/devcache.py)
+        self._resident = cfg.model == "mnist_cnn" and getattr(self.engine, "kind", "") == "native"
+        self.eval_cache = {"test": DeviceArrayCache(), "val": DeviceArrayCache()}
+        self._eval_y: Dict = {}
+        # --eval-metrics: the last event's global metrics per split; --ckpt-best
+        self.last_metrics: Dict[str, EvalMetrics] = {}
+        self.best_val_error = float("inf")
+        self.best_step: Optional[int] = None
 
     # ------------------------------------------------------------------ data
     def _prepare_data(self):
@@ -129,6 +152,8 @@ class Trainer:
                                    SplitSizes(self.world, rows * self.world, trows * self.world, 0))
         if self.shard.test_x.shape[0] < 1:
             raise ValueError("empty local test shard")
+        if cfg.ckpt_best and self.shard.val_x.shape[0] < 1:
+            raise ValueError("--ckpt-best: this rank's shard has no validation rows")
 
     def _make_engine(self):
         cfg = self.cfg
@@ -166,9 +191,91 @@ class Trainer:
         if self.device.type == "cuda":
             torch.cuda.synchronize(self.device)
 
-    def evaluate(self, dropout: Optional[bool] = None) -> float:
+    def _split(self, split: str):
+        if split == "test":
+            return self.shard.test_x, self.shard.test_y
+        if split == "val":
+            return self.shard.val_x, self.shard.val_y
+        raise ValueError(f"unknown split {split!r}; choose 'test' or 'val'")
+
+    def _labels_dev(self, split: str, y: np.ndarray) -> torch.Tensor:
+        """int32 device copy of a split's labels, uploaded once per array object"""
+        held = self._eval_y.get(split)
+        if held is None or held[0] is not y:
+            held = (y, torch.from_numpy(np.ascontiguousarray(y).astype(np.int32)).to(self.device))
+            self._eval_y[split] = held
+        return held[1]
+
+    def _engine_evaluate(self, split: str, dropout: Optional[bool], return_logits: bool = False):
+        x, y = self._split(split)
         d = self.cfg.eval_dropout if dropout is None else dropout
-        return self.engine.evaluate(self.shard.test_x, self.shard.test_y, dropout=d)
+        if self._resident:
+            x_dev = self.eval_cache[split].get(x, self.device)
+            return self.engine.evaluate(x, y, dropout=d, x_dev=x_dev,
+                                        y_dev=self._labels_dev(split, y),
+                                        return_logits=return_logits)
+        return self.engine.evaluate(x, y, dropout=d, return_logits=return_logits)
+
+    def evaluate(self, dropout: Optional[bool] = None) -> float:
+        return self._engine_evaluate("test", dropout)
+
+    def _split_metrics(self, split: str, dropout: Optional[bool] = None):
+        x, y = self._split(split)
+        if x.shape[0] < 1:
+            raise ValueError(f"this rank's {split} split is empty")
+        err, logits = self._engine_evaluate(split, dropout, return_logits=True)
+        labels = self._labels_dev(split, y) if self._resident else torch.from_numpy(
+            np.ascontiguousarray(y).astype(np.int64))
+        return err, Fn.eval_metrics(logits, labels)
+
+    def evaluate_metrics(self, split: str = "test", dropout: Optional[bool] = None) -> EvalMetrics:
+        """Metrics of this rank's rows of a split (utils/metrics.py): the
+        engine's evaluation logits through Fn.eval_metrics, so it holds for
+        every engine.  Global metrics are the sum over the ranks."""
+        return self._split_metrics(split, dropout)[1]
+
+    def _metrics_event(self, step: int, final: bool = False):
+        """--eval-metrics at an eval event: this rank's test error (the log
+        line's), the keys the event adds to its metrics record - the metrics
+        of the test and validation splits summed over the ranks - and rank 0's
+        extra log line.
+        --ckpt-best: the checkpoint is written here when the global validation
+        error improved (the same value, so the same branch, on every rank)."""
+        cfg = self.cfg
+        err, test = self._split_metrics("test")
+        parts = {"test": test}
+        if self.shard.val_x.shape[0] > 0:  # the same on every rank (5000 // world)
+            parts["val"] = self._split_metrics("val")[1]
+        packed = [m.pack() for m in parts.values()]
+        ints = np.concatenate([p[0] for p in packed])
+        sums = np.concatenate([p[1] for p in packed])
+        if self.world > 1:
+            with self.watchdog.guard(f"evaluation metrics all-reduce at step {step}"):
+                ints, sums = D.allreduce_sum_host_array(ints), D.allreduce_sum_host_array(sums)
+        k, per = test.classes, test.classes * (test.classes + 1) + 2
+        for i, name in enumerate(parts):
+            parts[name] = EvalMetrics.unpack(ints[i * per:(i + 1) * per], sums[i:i + 1], k)
+        self.last_metrics = parts
+        test, val = parts["test"], parts.get("val")
+        rec = {"test_loss": test.loss, "test_error_global": test.error,
+               "test_top3_error": test.topk_error(3)}
+        line = (f"[metrics] step {step}: test loss {test.loss:.4f}, error {test.error:.2f}%, "
+                f"top-3 error {test.topk_error(3):.2f}%")
+        if val is not None:
+            rec.update(val_error=val.error, val_loss=val.loss)
+            line += f"; validation loss {val.loss:.4f}, error {val.error:.2f}%"
+        if final:
+            rec.update(test_confusion=test.confusion.tolist(), test_rank_hist=test.rank_hist.tolist(),
+                       test_per_class_recall=test.to_json()["per_class_recall"])
+            if val is not None:
+                rec["val_confusion"] = val.confusion.tolist()
+        if cfg.ckpt_best:  # val is there: checked at start-up
+            if val.error < self.best_val_error:  # ties keep the earlier checkpoint
+                self.best_val_error, self.best_step = val.error, step
+                self.save_checkpoint(cfg.ckpt_best)
+            rec.update(best_val_error=self.best_val_error, best_step=self.best_step)
+            line += f" (best {self.best_val_error:.2f}% at step {self.best_step})"
+        return err, rec, line
 
     def eval_prediction(self, x: np.ndarray, dropout: Optional[bool] = None) -> torch.Tensor:
         """`eval_prediction = softmax(model(eval_data))` of the reference
@@ -257,11 +364,18 @@ class Trainer:
             ev = cfg.effective_eval_every()
             if ev and last % ev == 0:
                 t1 = time.perf_counter()
-                err = self.evaluate()
+                logged = last % (cfg.sync_every if cfg.reference_quirks else ev) == 0
+                extra: Dict = {}
+                if cfg.eval_metrics and logged:
+                    err, extra, mline = self._metrics_event(last)
+                else:
+                    err = self.evaluate()
                 eval_t += time.perf_counter() - t1
-                if last % (cfg.sync_every if cfg.reference_quirks else ev) == 0:
+                if logged:
                     emit(progress_line(self.rank, last, err), cfg.quiet)
-                    self.metrics.write(step=last, test_error=err, loss=eng.loss_value(),
+                    if extra and self.rank == 0:
+                        emit(mline, cfg.quiet)
+                    self.metrics.write(step=last, test_error=err, loss=eng.loss_value(), **extra,
                                        sync_schedule=self.sync_schedule(),
                                        lr=eng.lr(last), train_seconds=train_t,
                                        device_step_ms=timer.step_ms(),
@@ -285,7 +399,13 @@ class Trainer:
         if cfg.check_replicas:
             self.check_replicas(s - 1)
         t1 = time.perf_counter()
-        final_err = self.evaluate()
+        extra: Dict = {}
+        if cfg.eval_metrics:
+            final_err, extra, mline = self._metrics_event(s - 1, final=True)
+            if self.rank == 0:
+                emit(mline, cfg.quiet)
+        else:
+            final_err = self.evaluate()
         eval_t += time.perf_counter() - t1
         n_test = self.shard.test_x.shape[0]
         wrong_g = D.allreduce_sum_host(final_err * n_test / 100.0)
@@ -301,8 +421,10 @@ class Trainer:
             final_loss=eng.loss_value(), final_lr=eng.lr(max(0, s - 1)),
             device_step_ms=timer.step_ms(), engine=eng.kind,
             comm=getattr(self.comm, "kind", "none"), synthetic=self.shard.synthetic,
-            sync_schedule=self.sync_schedule(), xgmi_gate=self.comms.xgmi_status)
-        self.metrics.write(final=True, **summary.as_dict())
+            sync_schedule=self.sync_schedule(), xgmi_gate=self.comms.xgmi_status,
+            final_test_loss=extra.get("test_loss"), final_val_error=extra.get("val_error"),
+            final_val_loss=extra.get("val_loss"))
+        self.metrics.write(final=True, **summary.as_dict(), **extra)
         if cfg.ckpt:
             self.save_checkpoint(cfg.ckpt)
         self.metrics.close()

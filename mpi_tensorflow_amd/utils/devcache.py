@@ -29,10 +29,14 @@ class DeviceArrayCache:
         self._x: Optional[np.ndarray] = None
         self._key = None
         self._dev: Optional[torch.Tensor] = None
+        self.hits = 0  # get() calls answered by the resident copy
+        self.misses = 0  # ... and those that uploaded
 
     def get(self, x: np.ndarray, device: torch.device) -> torch.Tensor:
         if self._x is x and self._key == _key(x):
+            self.hits += 1
             return self._dev
+        self.misses += 1
         dev = torch.from_numpy(np.ascontiguousarray(x, np.float32)).to(device)
         self._x, self._key, self._dev = x, _key(x), dev
         return dev

@@ -10,7 +10,7 @@ module global, /root/reference/mpipy.py:14-21).  Here:
 with optional overrides (see --help): --epochs, --batch-size, --model
 {mnist_cnn,lenet5,resnet18}, --sync {grad,param_avg,none}, --sync-every,
 --eval-every, --synthetic, --ckpt/--resume, --metrics-jsonl,
---reference-quirks.  Log lines keep the reference's exact formats.
+--eval-metrics, --ckpt-best, --reference-quirks.  Log lines keep the reference's exact formats.
 """
 
 from __future__ import annotations
