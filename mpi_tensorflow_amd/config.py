@@ -83,6 +83,11 @@ DTYPES = ("fp32", "bf16")
 # fill:V.  MNIST: the normalised raw 0 pixel, (0 - 127.5) / 255; the others:
 # zero-padding of a centred image
 AUGMENT_FILL = {"mnist_cnn": -0.5, "lenet5": 0.0, "resnet18": 0.0}
+# --predict SRC: the words that name this configuration's own splits (anything
+# else is a file), and the largest test-time-augmentation shift (shift:3 with
+# flip is already 98 forwards per row)
+PREDICT_SPLITS = ("test", "val")
+MAX_TTA_SHIFT = 3
 
 
 def parse_augment(spec: str, model: str = "mnist_cnn"):
@@ -203,6 +208,16 @@ class TrainConfig:
     # checkpoint written whenever the global validation error improves
     # (strictly); implies eval_metrics
     ckpt_best: Optional[str] = None
+    # inference instead of training (runtime/predict.py): classify SRC - an
+    # IDX ubyte image file (raw or gzip), a .npy of uint8 / float32 rows, or
+    # "test" / "val" for this configuration's own split - with the checkpoint
+    # --resume; no Trainer is built
+    predict: Optional[str] = None
+    predict_labels: Optional[str] = None  # IDX / .npy labels of a file SRC: adds the metrics
+    predict_out: Optional[str] = None  # .npz of pred / topk_class / topk_prob [/ probs]
+    predict_topk: int = 3
+    predict_tta: Optional[str] = None  # test-time augmentation views, parse_augment syntax
+    predict_probs: bool = False
     quiet: bool = False
     # robustness: process-group / collective timeout (a dead rank turns into
     # an error instead of a hang) and a cross-replica consistency probe at
@@ -252,7 +267,36 @@ class TrainConfig:
             if self.effective_eval_every() == 0:
                 raise ValueError("--ckpt-best needs periodic evaluation (--eval-every > 0)")
             self.eval_metrics = True
+        if self.predict is not None:
+            self._validate_predict()
+        elif (self.predict_labels or self.predict_out or self.predict_tta or self.predict_probs):
+            raise ValueError("--predict-labels / --predict-out / --predict-tta / --predict-probs "
+                             "need --predict SRC")
         return self
+
+    def _validate_predict(self) -> None:
+        if not self.resume:
+            raise ValueError("--predict needs the checkpoint to predict with: --resume PATH")
+        if self.model == "resnet18":
+            raise ValueError("--predict does not support --model resnet18 (its forward lives in "
+                             "the autograd engine); use mnist_cnn or lenet5")
+        if not 1 <= self.predict_topk <= NUM_CLASSES:
+            raise ValueError(f"--predict-topk must be in [1, {NUM_CLASSES}], got "
+                             f"{self.predict_topk}")
+        if self.predict_tta is not None:
+            try:
+                K = parse_augment(self.predict_tta, self.model)[0]
+            except ValueError as e:
+                raise ValueError(f"--predict-tta: {e}") from None
+            if K > MAX_TTA_SHIFT:
+                raise ValueError(f"--predict-tta: shift:{K} is too many views; the largest "
+                                 f"shift is {MAX_TTA_SHIFT}")
+        src = self.predict
+        if src not in PREDICT_SPLITS and not src.endswith(".npy") and not os.path.isfile(src):
+            raise ValueError(f"--predict: {src!r} is neither a file (IDX ubyte or .npy) nor one "
+                             f"of the splits {PREDICT_SPLITS}")
+        if self.predict_labels and src in PREDICT_SPLITS:
+            raise ValueError(f"--predict-labels: --predict {src} brings its own labels")
 
     # quirk accessors ------------------------------------------------------
     @property
@@ -349,6 +393,21 @@ def build_arg_parser(prog: str = "mpipy.py") -> argparse.ArgumentParser:
     p.add_argument("--ckpt-best", default=None, metavar="PATH",
                    help="write the checkpoint there whenever the global validation error "
                         "improves (implies --eval-metrics; mnist_cnn, --eval-every > 0)")
+    p.add_argument("--predict", default=None, metavar="SRC",
+                   help="no training: classify SRC with the checkpoint --resume. SRC: an IDX "
+                        "ubyte image file (raw or gzip), a .npy of uint8 or float32 rows, or "
+                        "'test' / 'val' = this configuration's own split with its labels")
+    p.add_argument("--predict-labels", default=None, metavar="PATH",
+                   help="labels of a file SRC (IDX ubyte or .npy): adds error, loss, top-3 error "
+                        "and the confusion matrix")
+    p.add_argument("--predict-out", default=None, metavar="PATH.npz",
+                   help="write pred, topk_class and topk_prob there (rank 0)")
+    p.add_argument("--predict-topk", type=int, default=d.predict_topk, metavar="K")
+    p.add_argument("--predict-tta", default=None, metavar="SPEC",
+                   help="test-time augmentation: average the softmax over every view of "
+                        "shift:K[,flip][,fill:V] (K <= 3; (2K+1)^2 views, twice with flip)")
+    p.add_argument("--predict-probs", action="store_true",
+                   help="--predict-out also holds the class probabilities [n, 10]")
     p.add_argument("--quiet", action="store_true")
     p.add_argument("--collective-timeout-s", type=float, default=d.collective_timeout_s,
                    help="process-group / collective timeout (seconds)")

@@ -15,6 +15,7 @@
 #include "kernels/mnist.h"
 #include "kernels/mnist_bf16.h"
 #include "kernels/ops_generic.h"
+#include "kernels/predict.h"
 #include "kernels/shuffle.h"
 #include "lenet_executor.h"
 #include "mnist_executor.h"
@@ -761,6 +762,25 @@ PYBIND11_MODULE(_C, m) {
   }, py::arg("src_x"), py::arg("src_y"), py::arg("dst_x"), py::arg("dst_y"), py::arg("n"),
      py::arg("H"), py::arg("W"), py::arg("C"), py::arg("use_perm"), py::arg("perm_key"),
      py::arg("aug_key"), py::arg("K"), py::arg("flip"), py::arg("fill"), py::arg("st"));
+  // inference (kernels/predict.h): one view of the input rows, the prediction head
+  g.def("predict_prep", [](uintptr_t src, bool src_u8, uintptr_t dst, long long n, int H, int W,
+                           int C, int dy, int dx, bool flip, float fill, uintptr_t lut,
+                           uintptr_t st) {
+    predict::prep(P<const void>(src), src_u8, P<float>(dst), n, H, W, C, dy, dx, flip, fill,
+                  P<const float>(lut), S(st));
+    check_launch();
+  }, py::arg("src"), py::arg("src_u8"), py::arg("dst"), py::arg("n"), py::arg("H"), py::arg("W"),
+     py::arg("C"), py::arg("dy"), py::arg("dx"), py::arg("flip"), py::arg("fill"), py::arg("lut"),
+     py::arg("st"));
+  g.def("predict_head", [](uintptr_t logits, uintptr_t acc, int n, int C, int view, int views,
+                           int k, uintptr_t probs, uintptr_t scores, uintptr_t topk_class,
+                           uintptr_t topk_prob, uintptr_t st) {
+    predict::head(P<const float>(logits), P<float>(acc), n, C, view, views, k, P<float>(probs),
+                  P<float>(scores), P<int>(topk_class), P<float>(topk_prob), S(st));
+    check_launch();
+  }, py::arg("logits"), py::arg("acc"), py::arg("n"), py::arg("C"), py::arg("view"),
+     py::arg("views"), py::arg("k"), py::arg("probs"), py::arg("scores"), py::arg("topk_class"),
+     py::arg("topk_prob"), py::arg("st"));
 
   // ------------------------------------------------------------ executor
   py::class_<MnistPtrs>(m, "MnistPtrs")

@@ -913,6 +913,185 @@ def eval_metrics(logits: torch.Tensor, labels: torch.Tensor, out: Optional[EvalM
     return out.result() if own else out
 
 
+# -------------------------------------------------------------- inference --
+def predict_norm_table():
+    """The 256 normalised values of a uint8 pixel, by the expression of
+    utils/data.py extract_data: (float32(p) - 127.5) / 255 in float32."""
+    import numpy as np
+
+    return (np.arange(256, dtype=np.uint8).astype(np.float32) - 127.5) / 255
+
+
+_NORM_LUT = {}
+
+
+def _norm_lut(device: torch.device) -> torch.Tensor:
+    key = str(device)
+    if key not in _NORM_LUT:  # uploaded once per device
+        _NORM_LUT[key] = torch.from_numpy(predict_norm_table()).to(device)
+    return _NORM_LUT[key]
+
+
+def _predict_prep_oracle(src: torch.Tensor, dy: int, dx: int, flip: bool, fill: float):
+    from ..utils import rng
+
+    x = src.detach().cpu()
+    x = torch.from_numpy(predict_norm_table())[x.long()] if x.dtype == torch.uint8 else x.float()
+    n = x.shape[0]
+    v = rng.augment_np(x.numpy(), [dy] * n, [dx] * n, [bool(flip)] * n, fill)
+    return torch.from_numpy(v).to(src.device)
+
+
+def predict_prep(src: torch.Tensor, dy: int = 0, dx: int = 0, flip: bool = False,
+                 fill: float = 0.0, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """One view of [n, H, W, C] uint8 or fp32 rows as fp32 NHWC:
+    out[i, y, x, c] = norm(src[i, y + dy, (W - 1 - x if flip else x) + dx, c]),
+    `fill` where that pixel lies outside the image (utils/rng.py augment_np
+    with one draw for all rows); norm = predict_norm_table() for uint8, the
+    identity for fp32.  Native kernel on the GPU (predict.hip), torch / numpy
+    on the CPU oracle path.  `out` (fp32, contiguous, at least n rows): written
+    in place, its rows at n and above are left alone; returned as its first n rows."""
+    if src.dim() != 4 or src.dtype not in (torch.uint8, torch.float32):
+        raise ValueError("predict_prep takes [n, H, W, C] uint8 or float32 rows")
+    n, H, W, C = (int(s) for s in src.shape)
+    if abs(int(dy)) >= H or abs(int(dx)) >= W:
+        raise ValueError(f"predict_prep: shift ({dy}, {dx}) outside the {H} x {W} image")
+    if out is not None:
+        if (out.dtype != torch.float32 or not out.is_contiguous() or out.device != src.device
+                or out.numel() < n * H * W * C):
+            raise ValueError("predict_prep: `out` must be a contiguous fp32 tensor on the "
+                             "source's device with room for n rows")
+    if not src.is_cuda or _ORACLE:
+        v = _predict_prep_oracle(src, int(dy), int(dx), bool(flip), float(fill))
+        if out is None:
+            return v
+        dst = out.view(-1)[:n * H * W * C].view(n, H, W, C)
+        dst.copy_(v)
+        return dst
+    x = src.detach().contiguous()
+    if out is None:
+        out = torch.empty((n, H, W, C), dtype=torch.float32, device=x.device)
+    u8 = x.dtype == torch.uint8
+    if n > 0:
+        native().ops.predict_prep(ptr(x), u8, ptr(out), n, H, W, C, int(dy), int(dx), bool(flip),
+                                  float(fill), ptr(_norm_lut(x.device)) if u8 else 0,
+                                  stream_handle())
+    return out.view(-1)[:n * H * W * C].view(n, H, W, C)
+
+
+@dataclasses.dataclass
+class PredictHeadOut:
+    """predict_head's result: probs / scores [n, C] fp32, topk_class [n, k]
+    int32, topk_prob [n, k] fp32."""
+
+    probs: torch.Tensor
+    scores: torch.Tensor
+    topk_class: torch.Tensor
+    topk_prob: torch.Tensor
+
+
+def _topk_lowest_index(key: torch.Tensor, k: int) -> torch.Tensor:
+    """k rounds of "the lowest index among the maximal entries not taken yet"."""
+    key = key.clone()
+    n, c = key.shape
+    idx = torch.arange(c, dtype=torch.int64, device=key.device)
+    taken = torch.zeros_like(key, dtype=torch.bool)
+    out = torch.empty((n, k), dtype=torch.int64, device=key.device)
+    for r in range(k):
+        masked = torch.where(taken, torch.full_like(key, -float("inf")), key)
+        top = (masked == masked.max(dim=1, keepdim=True).values) & ~taken
+        pick = torch.where(top, idx, torch.full_like(idx, c)).min(dim=1).values
+        out[:, r] = pick
+        taken[torch.arange(n, device=key.device), pick] = True
+    return out
+
+
+def _predict_head_oracle(views, k: int) -> PredictHeadOut:
+    dev = views[0].device
+    xs = [v.detach().cpu().float() for v in views]
+    acc = torch.softmax(xs[0], dim=1)
+    for x in xs[1:]:  # in view order, fp32
+        acc = acc + torch.softmax(x, dim=1)
+    V = len(xs)
+    if V == 1:
+        probs, scores, key = acc, xs[0].clone(), xs[0]
+    else:
+        probs = acc / V
+        scores = torch.log(probs.clamp_min(torch.finfo(torch.float32).tiny))
+        key = probs
+    cls = _topk_lowest_index(key, k)
+    return PredictHeadOut(probs.to(dev), scores.to(dev), cls.to(torch.int32).to(dev),
+                          probs.gather(1, cls).to(dev))
+
+
+def predict_head(views, k: int = 1, out: Optional[PredictHeadOut] = None,
+                 acc: Optional[torch.Tensor] = None) -> PredictHeadOut:
+    """The prediction head over V views of the same n rows (a list of [n, C]
+    logits, or one tensor for V = 1; C <= 64, 1 <= k <= C):
+
+        probs  = mean over the views, in view order, of the fp32 max-subtracted softmax
+        scores = the logits (V = 1), else log(max(probs, FLT_MIN)): what
+                 eval_metrics reads as logits, with a finite loss
+        topk_class / topk_prob: k rounds of "the lowest index among the maximal
+                 keys not taken yet", key = logits (V = 1, so topk_class[:, 0] is
+                 the evaluation path's prediction) or probs (V > 1)
+
+    Native kernel on the GPU (predict.hip, one launch per view), torch on the
+    CPU oracle path.  `out` / `acc` ([n, C] fp32, V > 1): caller-owned buffers
+    written in place."""
+    if isinstance(views, torch.Tensor):
+        views = [views]
+    V = len(views)
+    if V < 1:
+        raise ValueError("predict_head needs at least one view")
+    n, c = int(views[0].shape[0]), int(views[0].shape[1])
+    if not 1 <= c <= 64:
+        raise ValueError(f"predict_head takes 1 to 64 classes, got {c}")
+    if not 1 <= int(k) <= c:
+        raise ValueError(f"predict_head: top-k needs 1 <= k <= {c}, got {k}")
+    k = int(k)
+    if any(tuple(v.shape) != (n, c) for v in views):
+        raise ValueError("predict_head: every view must be [n, C] logits of the same rows")
+    if not views[0].is_cuda or _ORACLE:
+        res = _predict_head_oracle(views, k)
+        if out is not None:
+            for f in dataclasses.fields(PredictHeadOut):
+                getattr(out, f.name).copy_(getattr(res, f.name))
+            return out
+        return res
+    dev = views[0].device
+    if out is None:
+        out = PredictHeadOut(torch.empty((n, c), device=dev), torch.empty((n, c), device=dev),
+                             torch.empty((n, k), dtype=torch.int32, device=dev),
+                             torch.empty((n, k), device=dev))
+    elif (tuple(out.probs.shape) != (n, c) or tuple(out.scores.shape) != (n, c)
+          or tuple(out.topk_class.shape) != (n, k) or tuple(out.topk_prob.shape) != (n, k)
+          or out.topk_class.dtype != torch.int32
+          or not all(getattr(out, f.name).is_contiguous() and getattr(out, f.name).device == dev
+                     for f in dataclasses.fields(PredictHeadOut))):
+        raise ValueError("predict_head: `out` does not fit these rows")
+    if V > 1:
+        if acc is None:
+            acc = torch.empty((n, c), device=dev)
+        elif (acc.dtype != torch.float32 or acc.numel() < n * c or not acc.is_contiguous()
+              or acc.device != dev):
+            raise ValueError("predict_head: `acc` must be a contiguous fp32 tensor of n * C")
+    for i, v in enumerate(views):
+        predict_head_view(v, i, V, k, out, acc)
+    return out
+
+
+def predict_head_view(logits: torch.Tensor, view: int, views: int, k: int, out: PredictHeadOut,
+                      acc: Optional[torch.Tensor]) -> None:
+    """One view's launch of the GPU head (no checks beyond the kernel's own:
+    runtime/predict.py calls it between the forward launches of the views)."""
+    x = logits.detach().float().contiguous()
+    n, c = int(x.shape[0]), int(x.shape[1])
+    native().ops.predict_head(ptr(x), ptr(acc) if views > 1 else 0, n, c, view, views, k,
+                              ptr(out.probs), ptr(out.scores), ptr(out.topk_class),
+                              ptr(out.topk_prob), stream_handle())
+
+
 # ---------------------------------------------------------------- pooling --
 class _MaxPoolFn(torch.autograd.Function):
     @staticmethod

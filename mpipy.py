@@ -11,6 +11,12 @@ with optional overrides (see --help): --epochs, --batch-size, --model
 {mnist_cnn,lenet5,resnet18}, --sync {grad,param_avg,none}, --sync-every,
 --eval-every, --synthetic, --ckpt/--resume, --metrics-jsonl,
 --eval-metrics, --ckpt-best, --reference-quirks.  Log lines keep the reference's exact formats.
+
+    python mpipy.py --resume best.npz --predict test           # evaluate a checkpoint
+    python mpipy.py --resume best.npz --predict digits.npy --predict-out p.npz
+
+classify instead of training (--predict SRC, --predict-labels, --predict-out,
+--predict-topk, --predict-tta, --predict-probs; runtime/predict.py).
 """
 
 from __future__ import annotations
@@ -30,6 +36,8 @@ from mpi_tensorflow_amd.config import (BATCH_SIZE, DATA_URL, IMAGE_SIZE, ITERATI
 
 def main(argv=None) -> int:
     cfg = config_from_args(argv)
+    if cfg.predict is not None:
+        return _predict(cfg)
     from mpi_tensorflow_amd.runtime.trainer import Trainer
 
     tr = Trainer(cfg)
@@ -39,6 +47,21 @@ def main(argv=None) -> int:
         sys.stdout.flush()
     from mpi_tensorflow_amd.parallel import dist as D
 
+    D.barrier()
+    D.shutdown()
+    return 0
+
+
+def _predict(cfg) -> int:
+    """--predict: no Trainer; rank 0 prints one JSON line {"predict": {...}}."""
+    from mpi_tensorflow_amd.parallel import dist as D
+    from mpi_tensorflow_amd.runtime.predict import predict_main
+
+    di = D.init(str(D.resolve_device(cfg.device)), timeout_s=cfg.collective_timeout_s)
+    rec = predict_main(cfg, di)
+    if di.rank == 0:
+        print(json.dumps(rec, sort_keys=True))
+        sys.stdout.flush()
     D.barrier()
     D.shutdown()
     return 0
