@@ -15,7 +15,7 @@ Gather-to-root weight averaging (`:121-137`).  Here a run gets:
   (`comm.xgmi_exactness_check`: integer data, bitwise equal to the exact sum
   and to `comm`'s sum).  The engine's auto-tune then also compares one trial
   step of each xGMI schedule with a step synced over `comm`
-  (runtime/mnist_engine.py `_xgmi_step_matches`, runtime/lenet_engine.py
+  (runtime/engine_common.py `xgmi_step_matches`, from both engines'
   `tune_schedule`).
 
 `health_vote` is the run-time half: the xGMI kernels never hang (a missing

@@ -1,6 +1,6 @@
 """Training engine for the generic models (LeNet-5, ResNet-18).
 
-Same contract as the MNIST engines (runtime/mnist_engine.py): flat fp32
+The contract of `engine_common.EngineBase`: flat fp32
 param / grad / momentum buffers, the reference's LR schedule and momentum
 SGD (/root/reference/mpipy.py:59-66), batch offset (step*B) % (N-B), DP by
 per-step gradient all-reduce of the flat grad buffer.
@@ -27,9 +27,9 @@ On CPU the same model runs through the PyTorch oracle ops.
 
 from __future__ import annotations
 
+import contextlib
 import dataclasses
 import gc
-
 from typing import Optional
 
 import numpy as np
@@ -43,22 +43,12 @@ from ..parallel.comm import DeviceComm, all_reduce_grads_
 from ..parallel.overlap import BUCKET_PLANS, BucketedAllReduce, SegmentedStep, plan_layout
 from ..utils.data import batch_offset
 from ..utils.devcache import DeviceArrayCache
-from ..utils.schedule import learning_rate
+from .engine_common import (TUNE_REPLAYS, EngineBase, StateSnapshot, all_ranks_ok, graph_sizes,
+                            pass_pieces, timed_replays)
 from .shuffle import make_shuffler
 
 
-class _null:
-    def __enter__(self):
-        return self
-
-    def __exit__(self, *exc):
-        return False
-
-
-TUNE_REPLAYS = 2  # timed graph replays per bucket-plan candidate (after one untimed)
-
-
-class GenericEngine:
+class GenericEngine(EngineBase):
     kind = "generic"
 
     def __init__(self, cfg: C.TrainConfig, train_x: np.ndarray, train_y: np.ndarray,
@@ -69,7 +59,6 @@ class GenericEngine:
         F.batch_norm, autograd) on `device` - a GPU-resident fp32 reference
         run of the same init, data and batch order (ops/functional.py
         oracle_mode); always fp32, eager, unsynced."""
-        self.cfg, self.device, self.rank, self.world, self.comm = cfg, device, rank, world, comm
         self.oracle = bool(oracle)
         self.bf16 = cfg.dtype == "bf16"
         if self.oracle and (self.bf16 or world > 1):
@@ -78,10 +67,7 @@ class GenericEngine:
             raise NotImplementedError("dtype bf16 needs the GPU kernels (bf16 MFMA convolutions)")
         self.model = make_model(cfg.model)
         self.layout = self.model.layout
-        self.B = cfg.batch_size
-        self.n_local = int(train_x.shape[0])
-        if self.n_local <= self.B:
-            raise ValueError("local shard must exceed the batch")
+        super().__init__(cfg, train_x.shape[0], device, rank, world, comm, force_sync)
         host = torch.zeros(self.layout.total)
         self.model.init_params(host, cfg.seed)
         self.params = host.to(device).requires_grad_(True)
@@ -95,10 +81,6 @@ class GenericEngine:
         self.bn = self.model.make_bn_state(device)
         self.train_x = torch.from_numpy(np.ascontiguousarray(train_x, np.float32)).to(device)
         self.train_y = torch.from_numpy(np.asarray(train_y).astype(np.int32)).to(device)
-        self.step = 0
-        self.grad_sync = cfg.sync == "grad" and world > 1 and comm is not None
-        if force_sync and comm is not None:  # exercise the collective path at world 1
-            self.grad_sync = True
         self.on_gpu = device.type == "cuda" and not self.oracle
         self.wcache = None
         self.use_graph = cfg.graph and self.on_gpu
@@ -106,6 +88,8 @@ class GenericEngine:
         self._graphs = {}
         self._graph_loss = {}
         self._warm = False
+        self._loss_t = None  # the last GPU step's loss (a device scalar, maybe a graph's)
+        self._lr_fresh = False  # lr_dev holds the LR of the step about to update
         self.loss_buf = torch.zeros(()).to(device)
         self._eval_x = DeviceArrayCache()
         self.bucketer = None
@@ -140,8 +124,7 @@ class GenericEngine:
         # train_y (runtime/shuffle.py; keyed by the rank of the dropout stream, Q14): the
         # HIP gather on the native path, the host permutation and transform on the
         # PyTorch paths
-        self.shuffler = make_shuffler(cfg, 0 if cfg.same_seed_all_ranks else rank, self.n_local,
-                                      self.train_x, self.train_y,
+        self.shuffler = make_shuffler(cfg, self.drop_rank, self.n_local, self.train_x, self.train_y,
                                       native=self._C if self.on_gpu else None,
                                       image_shape=tuple(self.train_x.shape[1:]))
         if self.shuffler is not None:
@@ -186,13 +169,12 @@ class GenericEngine:
         if self._tuned or self.bucketer is None or not self.use_graph:
             self._tuned = True
             return 0
-        from ..parallel import dist as D
         G = self.graph_steps
         host_step = self.step
         if self.shuffler is not None:  # the (discarded) trial steps read the current pass
             self.shuffler.ensure(self.step)
-        snap = (self.params.detach().clone(), self.mom.clone(), self.step_dev.clone(),
-                {k: (rm.clone(), rv.clone()) for k, (rm, rv) in self.bn.items()})
+        snap = StateSnapshot(self.params, self.mom, self.step_dev,
+                             *(t for rm_rv in self.bn.values() for t in rm_rv))
         self._warmup(3)  # the capture precondition; its steps are undone below too
         seen, best, steps = {}, None, 0
         for plan in BUCKET_PLANS:
@@ -203,30 +185,18 @@ class GenericEngine:
             seen[key] = plan
             self._set_bucket_plan(plan)
             g = self._graph(G)
-            if D.allreduce_max_host(0.0 if g is not None else 1.0) != 0.0:
+            if not all_ranks_ok(g is not None):
                 self.use_graph = False  # some rank could not capture: every rank runs eagerly
                 best = None
                 break
             g.replay()
-            t0 = torch.cuda.Event(enable_timing=True)
-            t1 = torch.cuda.Event(enable_timing=True)
-            t0.record()
-            for _ in range(TUNE_REPLAYS):
-                g.replay()
-            t1.record()
-            torch.cuda.synchronize(self.device)
+            us = timed_replays(g, TUNE_REPLAYS, G, self.device)
             steps += (1 + TUNE_REPLAYS) * G
-            us = D.allreduce_max_host(1000.0 * t0.elapsed_time(t1) / (TUNE_REPLAYS * G))
             self.tune_log[plan] = round(us, 1)
             if best is None or us < best[0]:
                 best = (us, plan)
         self._set_bucket_plan(best[1] if best is not None else "layout")
-        self.params.data.copy_(snap[0])
-        self.mom.copy_(snap[1])
-        self.step_dev.copy_(snap[2])
-        for k, (rm, rv) in snap[3].items():
-            self.bn[k][0].copy_(rm)
-            self.bn[k][1].copy_(rv)
+        snap.restore()
         if self.wcache is not None:  # the bf16 weight copies follow the restored weights
             self.wcache.refresh()
             self._wfresh = True
@@ -235,13 +205,6 @@ class GenericEngine:
         self._tuned = True
         self.tune_steps_run = steps
         return steps
-
-    def lr(self, step: Optional[int] = None) -> float:
-        s = self.step if step is None else step
-        return learning_rate(s, self.n_local, self.B, self.cfg.base_lr, self.cfg.lr_decay)
-
-    def sync_optimizer_state(self) -> None:
-        """Replicated optimizer state: nothing to gather."""
 
     def extra_state(self):
         """Non-trained model state saved with checkpoints: the BatchNorm
@@ -252,14 +215,8 @@ class GenericEngine:
             out[name + "/moving_variance"] = rv
         return out
 
-    def set_step(self, step: int) -> None:
-        self.step = int(step)
-        if self.on_gpu:
-            self.step_dev.copy_(torch.tensor([int(step)], dtype=torch.int64))
-
     def loss_value(self) -> float:
-        t = getattr(self, "_loss_t", None) if self.on_gpu else None
-        return float((t if t is not None else self.loss_buf).item())
+        return float((self._loss_t if self._loss_t is not None else self.loss_buf).item())
 
     def param_views(self):
         return self.layout.views(self.params.detach())
@@ -325,7 +282,7 @@ class GenericEngine:
         of this step ran since the last update)."""
         C_ = self._C
         s = stream_handle()
-        if not getattr(self, "_lr_fresh", False):
+        if not self._lr_fresh:
             C_.ops.lr_from_step(ptr(self.step_dev), self.n_local, self.B, self.cfg.base_lr,
                                 self.cfg.lr_decay, ptr(self.lr_dev), s)
         self._lr_fresh = False
@@ -436,7 +393,7 @@ class GenericEngine:
     def _host_state(self):
         """Host-side state a captured step changes (the bucketer resets its own
         per-step state in begin()): restored when a capture is abandoned."""
-        return (getattr(self, "_loss_t", None), self._wfresh, getattr(self, "_lr_fresh", False))
+        return (self._loss_t, self._wfresh, self._lr_fresh)
 
     def _capture_voted(self, err, host, what: str) -> bool:
         """Collective: a capture is kept only if it succeeded on EVERY rank
@@ -445,8 +402,7 @@ class GenericEngine:
         host state the aborted capture changed and trains eagerly."""
         ok = err is None
         if self.world > 1 and self.comm is not None:
-            from ..parallel import dist as D
-            ok = D.allreduce_max_host(0.0 if ok else 1.0) == 0.0
+            ok = all_ranks_ok(ok)
         if ok:
             return True
         why = err if err is not None else "it failed on another rank"
@@ -482,25 +438,19 @@ class GenericEngine:
         if not (self.on_gpu and self.use_graph) or k <= 0:
             return
         self._warmup(3)
-        G = self.graph_steps
-        if k >= G:
-            self._graph(G)
-        if k % G:
-            self._graph(k % G)
+        for n in graph_sizes(k, self.graph_steps):
+            self._graph(n)
 
     def train(self, k: int) -> None:
-        if self.shuffler is None or not self.on_gpu:  # (the CPU step checks its pass itself)
-            return self._train(k)
-        # k is cut at the pass boundaries here, whatever the caller asked for
-        for p, m in self.shuffler.segments(self.step, k):
-            self.shuffler.load(p)
+        # (the CPU step checks its pass itself)
+        for m in pass_pieces(self.shuffler if self.on_gpu else None, self.step, k):
             self._train(m)
 
     def _train(self, k: int) -> None:
         if k <= 0:
             return
         if not self.on_gpu:
-            with Fn.oracle_mode() if self.oracle else _null():
+            with Fn.oracle_mode() if self.oracle else contextlib.nullcontext():
                 for _ in range(k):
                     self._step_cpu()
                     self.step += 1
@@ -542,7 +492,7 @@ class GenericEngine:
         outs = []
         if not self.on_gpu:
             wrong = 0
-            with Fn.oracle_mode() if self.oracle else _null():
+            with Fn.oracle_mode() if self.oracle else contextlib.nullcontext():
                 for a in range(0, n, chunk):
                     xb = torch.from_numpy(np.ascontiguousarray(x[a:a + chunk], np.float32))
                     lg = self.model.forward(self.P, self.bn, xb.to(self.device), False)

@@ -1,14 +1,14 @@
 """Native LeNet-5 engine (BASELINE config 4) on the fused kernels of
 `csrc/kernels/lenet.hip` through the C++ `LenetExecutor`.
 
-Same state and step contract as the other engines (flat fp32 param / grad /
-momentum buffers in the parallel/flat.py layout, device step counter,
+State and step contract of `engine_common.EngineBase` (flat fp32 param /
+grad / momentum buffers in the parallel/flat.py layout, device step counter,
 reference LR schedule + momentum SGD of /root/reference/mpipy.py:59-66,
 batch offset (step * B) % (N - B) of :80, per-step gradient all-reduce for
 DP), but a training step is two kernel launches (one workgroup per image for
 the whole forward + backward, then the batch-level weight gradients + SGD)
 instead of the ~37 of the generic op-by-op path, and G steps are captured
-into one hipGraph.  The numerics oracle is the generic engine's CPU path
+into one hipGraph (`engine_common.GraphStepDriver`).  The numerics oracle is the generic engine's CPU path
 (models/generic.py LeNet5 on plain PyTorch ops).
 """
 
@@ -24,7 +24,8 @@ from ..models.generic import make_model
 from ..ops import native, ptr, stream_handle
 from ..parallel.comm import DeviceComm, XgmiDeviceComm
 from ..utils.devcache import DeviceArrayCache
-from ..utils.schedule import learning_rate
+from .engine_common import (TUNE_REPLAYS, EngineBase, GraphStepDriver, StateSnapshot,
+                            all_ranks_ok, timed_replays, xgmi_healthy, xgmi_step_matches)
 from .shuffle import make_shuffler
 
 # the executor's xGMI sync modes (csrc/lenet_executor.h XGMI_*)
@@ -35,7 +36,7 @@ _OFFSETS = (("c1w", "c1_w"), ("c1b", "c1_b"), ("c2w", "c2_w"), ("c2b", "c2_b"), 
             ("f1b", "f1_b"), ("f2w", "f2_w"), ("f2b", "f2_b"), ("f3w", "f3_w"), ("f3b", "f3_b"))
 
 
-class NativeLenetEngine:
+class NativeLenetEngine(GraphStepDriver, EngineBase):
     kind = "native-lenet5"
 
     def __init__(self, cfg: C.TrainConfig, train_x: np.ndarray, train_y: np.ndarray,
@@ -52,13 +53,9 @@ class NativeLenetEngine:
         if cfg.dtype != "fp32":
             raise NotImplementedError("the fused LeNet-5 kernels are fp32 (VALU convs over 3 / 6 "
                                       "channels); use the generic engine for bf16")
-        self.cfg, self.device, self.rank, self.world, self.comm = cfg, device, rank, world, comm
+        super().__init__(cfg, train_x.shape[0], device, rank, world, comm, force_sync)
         self.model = make_model("lenet5")
         self.layout = self.model.layout
-        self.B = cfg.batch_size
-        self.n_local = int(train_x.shape[0])
-        if self.n_local <= self.B:
-            raise ValueError("local shard must exceed the batch")
         if tuple(train_x.shape[1:]) != (32, 32, 3):
             raise ValueError(f"LeNet-5 input must be 32x32x3 NHWC, got {train_x.shape[1:]}")
         host = torch.zeros(self.layout.total)
@@ -71,21 +68,16 @@ class NativeLenetEngine:
         self._eval_x = DeviceArrayCache()
         self.train_x = torch.from_numpy(np.ascontiguousarray(train_x, np.float32)).to(dev)
         self.train_y = torch.from_numpy(np.asarray(train_y).astype(np.int32)).to(dev)
-        self.step = 0
         self.step_dev = torch.zeros(1, dtype=torch.int64, device=dev)
         self.lr_dev = torch.zeros(1, device=dev)
         self.correct_dev = torch.zeros(1, dtype=torch.int32, device=dev)
-        self.grad_sync = cfg.sync == "grad" and world > 1 and comm is not None
-        if force_sync and comm is not None:
-            self.grad_sync = True
         C_ = native()
         self._C = C_
         # cfg.shuffle / cfg.augment: the per-pass row order and shift / flip of the
         # working copy above (runtime/shuffle.py; keyed by the rank of the dropout
         # stream, Q14)
-        self.shuffler = make_shuffler(cfg, 0 if cfg.same_seed_all_ranks else rank, self.n_local,
-                                      self.train_x, self.train_y, native=C_,
-                                      image_shape=(32, 32, 3))
+        self.shuffler = make_shuffler(cfg, self.drop_rank, self.n_local, self.train_x, self.train_y,
+                                      native=C_, image_shape=(32, 32, 3))
         na, nd, nc = C_.lenet_buffer_floats(self.B)
         self.acts = torch.zeros(na, device=dev)
         self.deltas = torch.zeros(nd, device=dev)
@@ -160,10 +152,6 @@ class NativeLenetEngine:
         self._graphs: Dict[int, torch.cuda.CUDAGraph] = {}
 
     # ------------------------------------------------------------------ util
-    def lr(self, step: Optional[int] = None) -> float:
-        s = self.step if step is None else step
-        return learning_rate(s, self.n_local, self.B, self.cfg.base_lr, self.cfg.lr_decay)
-
     def sync_optimizer_state(self) -> None:
         """Replicated optimizer state: nothing to gather, except over the xGMI
         communicator's two-phase sync, whose fused all-reduce + SGD keeps each
@@ -190,18 +178,8 @@ class NativeLenetEngine:
             return {"two-phase": "xgmi", "push": "xgmi-push", "pull": "xgmi-pull"}[self.xgmi_mode]
         return "all-reduce"
 
-    def extra_state(self):
-        return {}
-
-    def set_step(self, step: int) -> None:
-        self.step = int(step)
-        self.step_dev.fill_(int(step))
-
     def loss_value(self) -> float:
         return float(self.loss_rows.mean().item())
-
-    def param_views(self):
-        return self.layout.views(self.params)
 
     # ------------------------------------------------------------------ step
     def _launch_one(self) -> None:
@@ -244,64 +222,41 @@ class NativeLenetEngine:
         checks).  Returns the trial steps run."""
         if self._tuned:
             return 0
-        from ..parallel import dist as D
-        from ..parallel.sync import replicas_identical
-        from .mnist_engine import TUNE_REPLAYS, XGMI_STEP_RTOL
         G = self.graph_steps
         if self.shuffler is not None:  # the (discarded) trial steps read the current pass
             self.shuffler.ensure(self.step)
-        snap = (self.params.clone(), self.mom.clone(), self.step_dev.clone())
+        snap = StateSnapshot(self.params, self.mom, self.step_dev)
         xh = self.xcomm.native_handle
-        cands = [("all-reduce", self._native_comm, "two-phase"), ("xgmi", xh, "two-phase"),
+        base = (self._native_comm, "two-phase")
+        cands = [("all-reduce",) + base, ("xgmi", xh, "two-phase"),
                  ("xgmi-push", xh, "push"), ("xgmi-pull", xh, "pull")]
         best, steps = None, 0
-
-        def restore():
-            self.params.copy_(snap[0])
-            self.mom.copy_(snap[1])
-            self.step_dev.copy_(snap[2])
-            torch.cuda.synchronize(self.device)
-
         for name, c, mode in cands:
             if c is not self._native_comm and self.xcomm is None:
                 self.tune_log[name] = None  # (the xGMI communicator timed out before)
                 continue
             self._set_sync(c, mode)
-            restore()
+            snap.restore(sync=True)
             g = self._graph(G)
-            if D.allreduce_max_host(0.0 if g is not None else 1.0) != 0.0:
+            if not all_ranks_ok(g is not None):
                 self.tune_log[name] = None
                 continue
             g.replay()
             torch.cuda.synchronize(self.device)
             steps += G
             if c is not self._native_comm:
-                why = None
-                if D.allreduce_max_host(float(self.xcomm.error())) != 0.0:
-                    why = "a peer barrier timed out"
-                else:
-                    self.sync_optimizer_state()
-                    if not (replicas_identical(self.params) and replicas_identical(self.mom)):
-                        why = "the replicas differ after the trial steps"
+                why = xgmi_healthy(self)
                 if why is None and not self.xcomm.emulated_comm:  # one eager step each
                     outs = []
-                    for cc, pp in ((c, mode), (self._native_comm, "two-phase")):
+                    for cc, pp in ((c, mode), base):
                         self._set_sync(cc, pp)
-                        restore()
+                        snap.restore(sync=True)
                         self._launch_one()
                         torch.cuda.synchronize(self.device)
                         outs.append(self.params.clone())
                     self._set_sync(c, mode)
-                    dx, ds = outs[0] - snap[0], outs[1] - snap[0]
-                    ref = float(ds.abs().max())
-                    err = float((dx - ds).abs().max())
-                    worst = D.allreduce_max_host(err / max(ref, 1e-30))
-                    bad = not (err <= XGMI_STEP_RTOL * ref)
-                    if D.allreduce_max_host(1.0 if bad else 0.0) != 0.0:
-                        why = (f"one trial step differs from the all-reduce's by {worst:.2e} of "
-                               f"the largest update (bound {XGMI_STEP_RTOL:g})")
-                    else:
-                        self.xgmi_step_check[name] = worst
+                    why = xgmi_step_matches(self, name, snap.saved[0], outs[0], outs[1],
+                                            "the all-reduce's")
                 if why is not None:
                     self.tune_log[name] = None
                     self.tune_reject[name] = why
@@ -310,65 +265,18 @@ class NativeLenetEngine:
                     if "timed out" in why:
                         self.xcomm = None  # never used again (its barriers stop waiting)
                     continue
-                restore()
-            t0 = torch.cuda.Event(enable_timing=True)
-            t1 = torch.cuda.Event(enable_timing=True)
-            t0.record()
-            for _ in range(TUNE_REPLAYS):
-                g.replay()
-            t1.record()
-            torch.cuda.synchronize(self.device)
+                snap.restore(sync=True)
+            us = timed_replays(g, TUNE_REPLAYS, G, self.device)
             steps += TUNE_REPLAYS * G
-            us = D.allreduce_max_host(1000.0 * t0.elapsed_time(t1) / (TUNE_REPLAYS * G))
             self.tune_log[name] = round(us, 2)
             if best is None or us < best[0]:
                 best = (us, c, mode)
         if best is None:
-            best = (0.0, self._native_comm, "two-phase")
+            best = (0.0,) + base
         self._set_sync(best[1], best[2])
-        restore()
+        snap.restore(sync=True)
         self._tuned = True
         return steps
-
-    def capture(self, k: int) -> None:
-        if self.use_graph and k > 0:
-            G = self.graph_steps
-            if k >= G:
-                self._graph(G)
-            if k % G:
-                self._graph(k % G)
-
-    def train(self, k: int) -> None:
-        if k <= 0:
-            return
-        if not self._tuned:  # side-effect free: restores the state it trained
-            self.tune_schedule()
-        if self.shuffler is None:
-            self._run_steps(k)
-        else:  # k is cut at the pass boundaries here, whatever the caller asked for
-            for p, m in self.shuffler.segments(self.step, k):
-                self.shuffler.load(p)
-                self._run_steps(m)
-        self.step += k
-
-    def _run_steps(self, k: int) -> None:
-        """k steps on the shard as it stands: graph replays, else eager launches."""
-        done = 0
-        if self.use_graph:
-            G = self.graph_steps
-            full, rem = divmod(k, G)
-            g = self._graph(G) if full else None
-            if g is not None:
-                for _ in range(full):
-                    g.replay()
-                done = full * G
-            if rem and self.use_graph:
-                g = self._graph(rem)
-                if g is not None:
-                    g.replay()
-                    done += rem
-        for _ in range(k - done):
-            self._launch_one()
 
     def forward_backward_only(self) -> None:
         """Forward + backward, weight grads into the flat grad buffer (no

@@ -1,8 +1,8 @@
 """Training-step engines for the MNIST CNN.
 
-Both engines own the same state - flat fp32 param / grad / momentum buffers
-(`parallel/flat.py` layout), a step counter and the rank's device-resident
-shard - and implement the same step semantics (reference `Cnn.run_process`
+Both engines own the same state (`engine_common.EngineBase`) - flat fp32
+param / grad / momentum buffers (`parallel/flat.py` layout), a step counter and
+the rank's device-resident shard - and implement the same step semantics (reference `Cnn.run_process`
 body, `/root/reference/mpipy.py:79-85`, + optimizer `:59-66`):
 
     offset = (step * B) % (N_local - B)                 (mpipy.py:80)
@@ -24,6 +24,7 @@ body, `/root/reference/mpipy.py:79-85`, + optimizer `:59-66`):
 from __future__ import annotations
 
 import math
+import time
 from typing import Dict, Optional
 
 import numpy as np
@@ -32,10 +33,13 @@ import torch
 from .. import config as C
 from ..models import mnist_cnn as M
 from ..ops import native, ptr, stream_handle
+from ..parallel import dist as D
 from ..parallel.comm import DeviceComm, XgmiDeviceComm, all_reduce_grads_
 from ..utils import rng
 from ..utils.data import batch_offset
-from ..utils.schedule import learning_rate
+from .engine_common import XGMI_STEP_RTOL  # noqa: F401  (re-exported: the tests' bound)
+from .engine_common import (TUNE_REPLAYS, EngineBase, GraphStepDriver, StateSnapshot, all_ranks_ok,
+                            timed_replays, xgmi_healthy, xgmi_step_matches)
 from .shuffle import make_shuffler
 
 # sync_schedule="auto": the single-communicator gradient-sync schedules
@@ -46,65 +50,27 @@ from .shuffle import make_shuffler
 # docs/PERF_NOTES.md) issues collectives on two RCCL communicators from two
 # streams at once; it is opt-in (--sync-schedule split) and never picked by
 # auto until it has run on a real multi-GPU node.
-TUNE_REPLAYS = 2
-# _xgmi_step_matches: max |update(xGMI) - update(serial)| / max |update(serial)|
-XGMI_STEP_RTOL = 1e-4
 
 
-class MnistEngineBase:
+class MnistEngineBase(EngineBase):
+    """The MNIST CNN's flat state on `device`, initialised from cfg.seed."""
+
     def __init__(self, cfg: C.TrainConfig, train_x: np.ndarray, train_y: np.ndarray,
                  device: torch.device, rank: int = 0, world: int = 1,
-                 comm: Optional[DeviceComm] = None):
-        self.cfg = cfg
-        self.device = device
-        self.rank, self.world = rank, world
-        self.comm = comm
+                 comm: Optional[DeviceComm] = None, force_sync: bool = False):
+        super().__init__(cfg, train_x.shape[0], device, rank, world, comm, force_sync)
         self.layout = M.layout()
-        self.B = cfg.batch_size
-        self.n_local = int(train_x.shape[0])
-        if self.n_local <= self.B:
-            raise ValueError(f"local shard of {self.n_local} rows must exceed batch {self.B}")
         self.params = torch.zeros(self.layout.total, dtype=torch.float32, device=device)
         self.grads = torch.zeros_like(self.params)
         self.mom = torch.zeros_like(self.params)
         host = torch.zeros(self.layout.total, dtype=torch.float32)
         M.init_params(host, self.layout, seed=cfg.seed)
         self.params.copy_(host)
-        self.step = 0  # host mirror of the global step (TF iter_)
         self.drop_seed = cfg.seed
-        self.drop_rank = 0 if cfg.same_seed_all_ranks else rank  # quirk Q14
-        self.grad_sync = cfg.sync == "grad" and world > 1 and comm is not None
-        self.shuffler = None  # cfg.shuffle / cfg.augment: the per-pass rows (runtime/shuffle.py)
-
-    # views -----------------------------------------------------------------
-    def param_views(self) -> Dict[str, torch.Tensor]:
-        return self.layout.views(self.params)
-
-    def lr(self, step: Optional[int] = None) -> float:
-        s = self.step if step is None else step
-        return learning_rate(s, self.n_local, self.B, self.cfg.base_lr, self.cfg.lr_decay)
 
     def l2_value(self) -> float:
         p = self.param_views()
         return float(self.cfg.l2 * M.l2_term(p).item())
-
-    def state_tensors(self):
-        return self.params, self.mom
-
-    def sync_optimizer_state(self) -> None:
-        """Makes `mom` whole on every rank (a sharded optimizer keeps only
-        its own shard current); no-op for replicated optimizers."""
-
-    def extra_state(self):
-        """Non-trained state saved with checkpoints (none for this model)."""
-        return {}
-
-    def set_step(self, step: int) -> None:
-        self.step = int(step)
-
-    def synchronize(self) -> None:
-        if self.device.type == "cuda":
-            torch.cuda.synchronize(self.device)
 
 
 class TorchMnistEngine(MnistEngineBase):
@@ -182,7 +148,7 @@ class TorchMnistEngine(MnistEngineBase):
         return err
 
 
-class NativeMnistEngine(MnistEngineBase):
+class NativeMnistEngine(GraphStepDriver, MnistEngineBase):
     """fused HIP kernels + C++ executor + hipGraph replay (MI355X); fp32
     (v_mfma_f32_32x32x2_f32) or bf16 (v_mfma_f32_32x32x16_bf16, fp32 master
     weights / grads / momentum) per cfg.dtype."""
@@ -205,9 +171,7 @@ class NativeMnistEngine(MnistEngineBase):
         LDS.  Equal in isolation (8.0 vs 8.3 us), but 3 us SLOWER in the step
         (10.0 vs 6.9 us: the 4-byte scattered a2t stores of 256 blocks leave
         partial lines in every XCD's L2), so off (docs/PERF_NOTES.md)."""
-        super().__init__(cfg, train_x, train_y, device, rank, world, comm)
-        if force_sync and comm is not None:  # exercise the collective path at world 1
-            self.grad_sync = True
+        super().__init__(cfg, train_x, train_y, device, rank, world, comm, force_sync)
         if device.type != "cuda":
             raise RuntimeError("NativeMnistEngine needs a GPU")
         C_ = native()
@@ -389,10 +353,6 @@ class NativeMnistEngine(MnistEngineBase):
                 self._native_comm2.all_reduce(g, g, n, 7, 0, hs)
             torch.cuda.synchronize(dev)
 
-    def set_step(self, step: int) -> None:
-        super().set_step(step)
-        self.step_dev.fill_(int(step))
-
     def _pick_schedule(self, name: str, nranks: int) -> int:
         E = self._C.MnistExecutor
         if name == "buckets":
@@ -432,12 +392,11 @@ class NativeMnistEngine(MnistEngineBase):
         if not self.grad_sync:
             return "none"
         E = self._C.MnistExecutor
-        return {E.SCHED_SHARDED_FC: "sharded", E.SCHED_SPLIT: "split",
-                E.SCHED_FACTORS: "factors", E.SCHED_SERIAL: "serial",
-                E.SCHED_DEFER: "defer", E.SCHED_XGMI: "xgmi",
-                E.SCHED_XGMI_STEP: "xgmi-step", E.SCHED_XGMI_FAC: "xgmi-fac"}.get(
-                    self.exe.schedule,
-                                                                           "buckets")
+        names = {E.SCHED_SHARDED_FC: "sharded", E.SCHED_SPLIT: "split",
+                 E.SCHED_FACTORS: "factors", E.SCHED_SERIAL: "serial",
+                 E.SCHED_DEFER: "defer", E.SCHED_XGMI: "xgmi",
+                 E.SCHED_XGMI_STEP: "xgmi-step", E.SCHED_XGMI_FAC: "xgmi-fac"}
+        return names.get(self.exe.schedule, "buckets")
 
     def sync_optimizer_state(self) -> None:
         if self.grad_sync:
@@ -519,20 +478,11 @@ class NativeMnistEngine(MnistEngineBase):
         number of trial steps run."""
         if self._tuned:
             return 0
-        from ..parallel import dist as D
         E = self._C.MnistExecutor
         G = self.graph_steps
         steps = 0
         best = None
-        self.exe.join(stream_handle())
-        if self.shuffler is not None:
-            # the trial steps read the order of the pass they start in (they are
-            # discarded; the working copy is what the step restored to reads)
-            self.shuffler.ensure(self.step)
-        # the candidates' steps take the derived weights (Winograd transforms,
-        # bf16 shadows) as current: derive them from the weights first
-        self.exe.refresh_shadows(stream_handle())
-        snap = (self.params.clone(), self.mom.clone(), self.step_dev.clone())
+        snap = self._trial_snapshot()
         cands = self._tune_candidates()
         xgmi_scheds = (E.SCHED_XGMI, E.SCHED_XGMI_STEP, E.SCHED_XGMI_FAC)
         xgmi_dead = False
@@ -548,8 +498,7 @@ class NativeMnistEngine(MnistEngineBase):
                                        else sched == E.SCHED_BUCKETS))
             # the decision must be collective: a candidate any rank could not
             # capture is dropped on every rank
-            ok = D.allreduce_max_host(0.0 if g is not None else 1.0) == 0.0
-            if not ok:
+            if not all_ranks_ok(g is not None):
                 if sched == E.SCHED_BUCKETS:  # no graphs at all: keep buckets, eager
                     break
                 self.tune_log[name] = None
@@ -557,9 +506,9 @@ class NativeMnistEngine(MnistEngineBase):
             g.replay()
             torch.cuda.synchronize(self.device)
             if uses_xgmi:
-                why = self._xgmi_healthy()
+                why = xgmi_healthy(self)
                 if why is None and sched in xgmi_scheds:
-                    why = self._xgmi_step_matches(sched, snap)
+                    why = self._xgmi_step_matches(sched, name, snap)
                 if why is not None:
                     self.tune_log[name] = None  # never pick it
                     self.tune_reject[name] = why
@@ -573,15 +522,8 @@ class NativeMnistEngine(MnistEngineBase):
                         # RCCL trains on; the dead xGMI comm leaves the health votes
                         self.xcomm = None
                     continue
-            t0 = torch.cuda.Event(enable_timing=True)
-            t1 = torch.cuda.Event(enable_timing=True)
-            t0.record()
-            for _ in range(TUNE_REPLAYS):
-                g.replay()
-            t1.record()
-            torch.cuda.synchronize(self.device)
+            us = timed_replays(g, TUNE_REPLAYS, G, self.device)
             steps += (1 + TUNE_REPLAYS) * G
-            us = D.allreduce_max_host(1000.0 * t0.elapsed_time(t1) / (TUNE_REPLAYS * G))
             self.tune_log[name] = round(us, 2)
             if best is None or us < best[0]:
                 best = (us, sched)
@@ -590,76 +532,51 @@ class NativeMnistEngine(MnistEngineBase):
                                + "; ".join(f"{k}: {v}" for k, v in self.tune_reject.items()))
         self._set_schedule(best[1] if best is not None else E.SCHED_BUCKETS)
         self.exe.join(stream_handle())
-        self.params.copy_(snap[0])
-        self.mom.copy_(snap[1])
-        self.step_dev.copy_(snap[2])
-        torch.cuda.synchronize(self.device)
+        snap.restore(sync=True)
         self._tuned = True
         self.tune_steps_run = steps
         return steps
 
-    def _xgmi_healthy(self) -> Optional[str]:
-        """Collective: None when no rank's xGMI barrier timed out (the device
-        kernels never hang: a missing peer sets a sticky error bit instead)
-        and the replicas agree bit for bit after the trial steps, else why."""
-        from ..parallel import dist as D
-        from ..parallel.sync import replicas_identical
-        bad = self.xcomm.error() if self.xcomm is not None else 0
-        if D.allreduce_max_host(float(bad)) != 0.0:
-            return "a peer barrier timed out"
-        if self.xcomm is None or self.xcomm.emulated_comm:
-            return None
-        # replicas must agree bit for bit after the trial steps (a lost or torn
-        # peer read would show here): gather the sharded momentum and compare
-        self.sync_optimizer_state()
-        torch.cuda.synchronize(self.device)
-        if not (replicas_identical(self.params) and replicas_identical(self.mom)):
-            return "the replicas differ after the trial steps"
-        return None
+    def _trial_snapshot(self) -> StateSnapshot:
+        """The state that steps which are to be discarded start from, and are
+        undone to (tune_schedule, prewarm_train)."""
+        self.exe.join(stream_handle())
+        if self.shuffler is not None:
+            # the trial steps read the order of the pass they start in (they are
+            # discarded; the working copy is what the step restored to reads)
+            self.shuffler.ensure(self.step)
+        # the trial steps take the derived weights (Winograd transforms, bf16
+        # shadows) as current: derive them from the weights first
+        self.exe.refresh_shadows(stream_handle())
+        return StateSnapshot(self.params, self.mom, self.step_dev)
 
-    def _xgmi_step_matches(self, sched: int, snap) -> Optional[str]:
+    def _xgmi_step_matches(self, sched: int, name: str, snap: StateSnapshot) -> Optional[str]:
         """Collective: one eager step of the xGMI schedule `sched` against one
         eager step of the serial schedule over the other communicator (RCCL;
         the xGMI comm's exactness-checked all-reduce when it is the only one),
-        both from the state `snap`.  Identical replicas cannot reveal a
-        wrong-but-consistent reduction (every rank gathers the same wrong
-        segments), this can: the two parameter updates must agree to
-        XGMI_STEP_RTOL of the largest update (rank-order vs RCCL summation is
-        ~1e-7; a rank left out of the sum is ~1/N).  None = match, else why.
-        The state is restored to `snap` afterwards.  Emulated communicators
-        are not compared (their numerics are not those of N ranks)."""
-        from ..parallel import dist as D
+        both from the state `snap`, which is restored afterwards; the bound is
+        engine_common.xgmi_step_matches.  Emulated communicators are not
+        compared (their numerics are not those of N ranks)."""
         if self.xcomm is None or self.xcomm.emulated_comm:
             return None
-        E = self._C.MnistExecutor
         s = stream_handle()
-        outs = []
-        for sc in (sched, E.SCHED_SERIAL):
+
+        def from_snap(sc):
             self._set_schedule(sc)
-            self.params.copy_(snap[0])
-            self.mom.copy_(snap[1])
-            self.step_dev.copy_(snap[2])
+            snap.restore()
             self.exe.refresh_shadows(s)
+
+        outs = []
+        for sc in (sched, self._C.MnistExecutor.SCHED_SERIAL):
+            from_snap(sc)
             self._launch_one()
             self.exe.join(s)
             torch.cuda.synchronize(self.device)
             outs.append(self.params.clone())
-        self._set_schedule(sched)
-        self.params.copy_(snap[0])
-        self.mom.copy_(snap[1])
-        self.step_dev.copy_(snap[2])
-        self.exe.refresh_shadows(s)
+        from_snap(sched)
         torch.cuda.synchronize(self.device)
-        dx, ds = outs[0] - snap[0], outs[1] - snap[0]
-        ref = float(ds.abs().max())
-        err = float((dx - ds).abs().max())
-        bad = not (err <= XGMI_STEP_RTOL * ref) or not math.isfinite(err)
-        worst = D.allreduce_max_host(err / max(ref, 1e-30))
-        if D.allreduce_max_host(1.0 if bad else 0.0) != 0.0:
-            return (f"one trial step differs from the serial schedule's by {worst:.2e} of the "
-                    f"largest update (bound {XGMI_STEP_RTOL:g})")
-        self.xgmi_step_check[self.sync_schedule] = worst
-        return None
+        return xgmi_step_matches(self, name, snap.saved[0], outs[0], outs[1],
+                                 "the serial schedule's")
 
     def prewarm_train(self, ms: float) -> float:
         """Untimed, side-effect-free training replays for ~`ms` of wall time
@@ -671,20 +588,13 @@ class NativeMnistEngine(MnistEngineBase):
         Returns the wall time spent (ms)."""
         if ms <= 0 or not self.use_graph:
             return 0.0
-        import time
-
-        from ..parallel import dist as D
         if not self._tuned:
             self.tune_schedule()
         g = self._graph(self.graph_steps)
         if g is None:
             return 0.0
         t_start = time.perf_counter()
-        self.exe.join(stream_handle())
-        if self.shuffler is not None:
-            self.shuffler.ensure(self.step)
-        self.exe.refresh_shadows(stream_handle())
-        snap = (self.params.clone(), self.mom.clone(), self.step_dev.clone())
+        snap = self._trial_snapshot()
         t0 = time.perf_counter()
         g.replay()
         torch.cuda.synchronize(self.device)
@@ -693,17 +603,11 @@ class NativeMnistEngine(MnistEngineBase):
         for _ in range(reps - 1):
             g.replay()
         self.exe.join(stream_handle())
-        self.params.copy_(snap[0])
-        self.mom.copy_(snap[1])
-        self.step_dev.copy_(snap[2])
-        torch.cuda.synchronize(self.device)
+        snap.restore(sync=True)
         return round(1000.0 * (time.perf_counter() - t_start), 1)
 
-    def train(self, k: int) -> None:
-        if k <= 0:
-            return
-        if not self._tuned:  # side-effect free: restores the state it trained
-            self.tune_schedule()
+    # hooks of GraphStepDriver.train
+    def _before_steps(self) -> None:
         # the steps' SGD launches keep the derived weights (Winograd transforms,
         # bf16 shadows) current for the next step; they are re-derived from the
         # master weights only when something outside the steps changed those
@@ -712,46 +616,13 @@ class NativeMnistEngine(MnistEngineBase):
         # writes do not).  Skipping the launch keeps it out of short timed runs.
         if self._derived_ver != self.params._version:
             self.exe.refresh_shadows(stream_handle())
-        if self.shuffler is None:
-            self._run_steps(k)
-        else:
-            # k is cut at the pass boundaries here, whatever the caller asked
-            # for; the pieces reuse the per-length graph cache
-            for p, m in self.shuffler.segments(self.step, k):
-                self.exe.join(stream_handle())  # no earlier step still in flight on the comm stream
-                self.shuffler.load(p)
-                self._run_steps(m)
+
+    def _before_pass_load(self) -> None:
+        self.exe.join(stream_handle())  # no earlier step still in flight on the comm stream
+
+    def _after_steps(self) -> None:
         self.exe.join(stream_handle())
-        self.step += k
         self._derived_ver = self.params._version
-
-    def _run_steps(self, k: int) -> None:
-        """k steps on the shard as it stands: graph replays, else eager launches."""
-        done = 0
-        if self.use_graph:
-            G = self.graph_steps
-            full, rem = divmod(k, G)
-            g = self._graph(G) if full else None
-            if g is not None:
-                for _ in range(full):
-                    g.replay()
-                done = full * G
-            if rem and self.use_graph:
-                g = self._graph(rem)
-                if g is not None:
-                    g.replay()
-                    done += rem
-        for _ in range(k - done):  # eager (no graphs, or capture unavailable)
-            self._launch_one()
-
-    def capture(self, k: int) -> None:
-        """Pre-captures the graphs `train(k)` will replay (outside timing)."""
-        if self.use_graph:
-            G = self.graph_steps
-            if k >= G:
-                self._graph(G)
-            if k % G:
-                self._graph(k % G)
 
     def forward_backward_only(self) -> None:
         """Forward + backward into the flat grad buffer; no sync, no SGD, no
