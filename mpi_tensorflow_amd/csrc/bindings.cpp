@@ -275,6 +275,34 @@ PYBIND11_MODULE(_C, m) {
   k.def("set_sgd_prof", [](uintptr_t p) {
     mnist::set_sgd_prof(reinterpret_cast<unsigned long long*>(p));
   });
+  k.def("set_fc_prof", [](uintptr_t p) {
+    mnist::set_fc_prof(reinterpret_cast<unsigned long long*>(p));
+  });
+  k.def("set_fc_chain", &mnist::set_fc_chain);
+  k.def("fc_chain", &mnist::fc_chain);
+  k.attr("FC_CHAIN_HEAD") = mnist::FC_CHAIN_HEAD;
+  k.attr("FC_CHAIN_FWD") = mnist::FC_CHAIN_FWD;
+  k.attr("FC_CHAIN_FWD_LOADS") = mnist::FC_CHAIN_FWD_LOADS;
+  // the train head with every argument (padded batch, bf16 operand outputs)
+  k.def("fc_head_train_full",
+        [](uintptr_t part, uintptr_t b3, uintptr_t w4, uintptr_t b4, uintptr_t labels, int n_local,
+           uintptr_t step, int batch, float keep, uint32_t seed, uint32_t rank, float base_lr,
+           float decay, uintptr_t hd, uintptr_t dh, uintptr_t dlog, uintptr_t loss_rows,
+           uintptr_t lr_out, uintptr_t correct, uintptr_t s, uintptr_t dh16, uintptr_t dht16,
+           int splits, int lbatch) {
+          mnist::launch_fc_head_train(P<const float>(part), P<const float>(b3), P<const float>(w4),
+                                      P<const float>(b4), P<const int>(labels), n_local,
+                                      P<const long long>(step), batch, keep, seed, rank, base_lr,
+                                      decay, P<float>(hd), P<float>(dh), P<float>(dlog),
+                                      P<float>(loss_rows), P<float>(lr_out), P<int>(correct), S(s),
+                                      P<uint16_t>(dh16), P<uint16_t>(dht16), splits, lbatch);
+          check_launch();
+        },
+        py::arg("part"), py::arg("b3"), py::arg("w4"), py::arg("b4"), py::arg("labels"),
+        py::arg("n_local"), py::arg("step"), py::arg("batch"), py::arg("keep"), py::arg("seed"),
+        py::arg("rank"), py::arg("base_lr"), py::arg("decay"), py::arg("hd"), py::arg("dh"),
+        py::arg("dlog"), py::arg("loss_rows"), py::arg("lr_out"), py::arg("correct"), py::arg("s"),
+        py::arg("dh16"), py::arg("dht16"), py::arg("splits"), py::arg("lbatch"));
   k.def("set_conv2_bwd_prof_bf16", [](uintptr_t p) {
     mnist16::set_conv2_bwd_prof(reinterpret_cast<unsigned long long*>(p));
   });

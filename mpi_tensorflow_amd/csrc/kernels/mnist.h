@@ -135,6 +135,21 @@ void launch_fc_head_train(const float* part, const float* b3, const float* w4, c
                           float* lr_out, int* correct, hipStream_t s, uint16_t* dh16 = nullptr,
                           uint16_t* dht16 = nullptr, int splits = 14,  // slabs in part
                           int lbatch = 0);
+// A/B of the shorter FC-chain forms (mnist.hip): a mask of the forms the
+// launchers take; the older form of each stays selectable on the same build.
+// mask < 0: back to the default.  Not captured: a graph keeps what it recorded.
+constexpr int FC_CHAIN_HEAD = 1;  // fc_head_train2_kernel
+constexpr int FC_CHAIN_FWD = 4;   // fc1_fwd_t_kernel<SPREAD>
+constexpr int FC_CHAIN_FWD_LOADS = 8;  // fc1_fwd_t_kernel<, UPFRONT>
+constexpr int FC_CHAIN_DEFAULT = FC_CHAIN_HEAD | FC_CHAIN_FWD | FC_CHAIN_FWD_LOADS;
+void set_fc_chain(int mask);
+int fc_chain();
+// labs: per-block [start, end] 100 MHz clock stamps of the three FC launches
+// into p: 3 regions (fc1 forward, head, fc1 backward) of 2 x 1024 u64, block
+// slots in logical (role) order; zero it before a step; null turns them off
+// (fc1_fwd_kernel / fc1_bwd_kernel: a PROF instantiation, so that the step's
+// own kernels carry no stamp code; the head and fc1_fwd_t: a null pointer)
+void set_fc_prof(unsigned long long* p);
 // lbatch (padded step, 0: = batch): rows >= lbatch are pad rows - dlog / dh /
 // dh16 / dht16 exactly zero, loss_rows 0, not counted in `correct`; the valid
 // rows' dlog is scaled by 1 / lbatch and the offset and LR epoch use lbatch

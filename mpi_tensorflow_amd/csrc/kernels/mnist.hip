@@ -34,6 +34,23 @@
 
 namespace mnist {
 
+// labs (set_fc_prof): per-block [start, end] of the constant 100 MHz clock for
+// the three FC launches, FC_PROF_SLOTS blocks each: the start of wave 0, the
+// latest end over the block's waves (the buffer is zeroed between launches)
+constexpr int FC_PROF_SLOTS = 1024;
+struct FcStamp {
+  unsigned long long* p;
+  unsigned long long t0;
+  __device__ __forceinline__ explicit FcStamp(unsigned long long* prof, int blk)
+      : p(prof && blk < FC_PROF_SLOTS ? prof + 2 * blk : nullptr),
+        t0(p ? __builtin_amdgcn_s_memrealtime() : 0ull) {}
+  __device__ __forceinline__ ~FcStamp() {
+    if (p && (threadIdx.x & 63) == 0) {
+      if (threadIdx.x == 0) p[0] = t0;
+      atomicMax(p + 1, (unsigned long long)__builtin_amdgcn_s_memrealtime());
+    }
+  }
+};
 
 // ----------------------------------------------------------- geometry ----
 template <int H_, int W_, int CIN_, int COUT_, int KS_, int PAD_, int BK_>
@@ -184,14 +201,17 @@ struct Fc1FwdProb {
 };
 
 // train: split-K partial slabs part[z][m][n]; eval: h = relu(acc + b) (+dropout)
-template <int WM, int WN, int WK, int BK, bool EVAL, int ONESHOT_KT = 0>
+// PROF (labs): block stamps into prof; off, the stamp folds away entirely
+template <int WM, int WN, int WK, int BK, bool EVAL, int ONESHOT_KT = 0, bool PROF = false>
 __global__ __launch_bounds__(64 * WM * WN * WK) void fc1_fwd_kernel(
     const float* __restrict__ a, const float* __restrict__ w, const float* __restrict__ bias,
-    float* __restrict__ out, int M, int kchunk, uint32_t drop_key, float keep_prob) {
+    float* __restrict__ out, int M, int kchunk, uint32_t drop_key, float keep_prob,
+    unsigned long long* __restrict__ prof) {
   using CF = gemm::Cfg<WM, WN, WK, BK, true, true>;
   constexpr int SM1 = ONESHOT_KT > 0 ? ONESHOT_KT * CF::STAGE_FLOATS : CF::SMEM_FLOATS;
   constexpr int SM = SM1 > CF::SMEM_FLOATS_RED ? SM1 : CF::SMEM_FLOATS_RED;
   __shared__ float smem[SM];
+  FcStamp stamp(PROF ? prof : nullptr, blockIdx.y * gridDim.x + blockIdx.x);
   Fc1FwdProb p{{a, FC1_IN, M}, w};
   const int mt = (M + CF::BM - 1) / CF::BM;
   const int z = blockIdx.y;
@@ -238,10 +258,20 @@ constexpr int FC1T_SPLITS = 8;
 constexpr int FC1T_KW = FC1_IN / FC1T_SPLITS / 4;  // 98 features per wave
 static_assert(FC1T_KW % 2 == 0 && FC1_IN % (FC1T_SPLITS * 4) == 0, "fc1_fwd_t split");
 
+// SPREAD: every wave leaves its partial tile in LDS and finishes 4 of the 16
+// accumulator rows (sum over the waves in wave order, as wave 0 alone forms
+// it with SPREAD off - the same bits - and a quarter of the stores each)
+// UPFRONT: a scheduling barrier between the operand loads and the products.
+// Without it the compiler keeps only 12 - 17 of the 98 loads in flight and
+// interleaves the rest with the MFMA chain in groups of 8 behind
+// s_waitcnt vmcnt(1): a dozen exposed L2 round trips a wave, not one.
+template <bool SPREAD, bool UPFRONT>
 __global__ __launch_bounds__(256) void fc1_fwd_t_kernel(const float* __restrict__ a2t,
                                                         const float* __restrict__ w,
-                                                        int batch, float* __restrict__ part) {
-  __shared__ float red[3][16][64];
+                                                        int batch, float* __restrict__ part,
+                                                        unsigned long long* __restrict__ prof) {
+  __shared__ float red[SPREAD ? 4 : 3][16][64];
+  FcStamp stamp(prof, blockIdx.y * gridDim.x + blockIdx.x);
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, i = lane & 31, h = lane >> 5;
   const int nt = blockIdx.x % (FC1_OUT / 32), bt = blockIdx.x / (FC1_OUT / 32);
   const int z = blockIdx.y;
@@ -256,6 +286,7 @@ __global__ __launch_bounds__(256) void fc1_fwd_t_kernel(const float* __restrict_
     av[t] = ap[(size_t)2 * t * batch];
     bv[t] = bp[(size_t)2 * t * FC1_OUT];
   }
+  if constexpr (UPFRONT) __builtin_amdgcn_sched_barrier(0);
   f32x16 c0 = zero16(), c1 = zero16();
 #pragma unroll
   for (int t = 0; t < ST; ++t) {
@@ -266,17 +297,30 @@ __global__ __launch_bounds__(256) void fc1_fwd_t_kernel(const float* __restrict_
   }
 #pragma unroll
   for (int r = 0; r < 16; ++r) c0[r] += c1[r];
-  if (wave > 0) {
+  if constexpr (SPREAD) {
 #pragma unroll
-    for (int r = 0; r < 16; ++r) red[wave - 1][r][lane] = c0[r];
-  }
-  __syncthreads();
-  if (wave == 0) {
+    for (int r = 0; r < 16; ++r) red[wave][r][lane] = c0[r];
+    __syncthreads();
 #pragma unroll
-    for (int r = 0; r < 16; ++r) {
-      const float v = c0[r] + red[0][r][lane] + red[1][r][lane] + red[2][r][lane];
+    for (int j = 0; j < 4; ++j) {
+      const int r = 4 * wave + j;
+      const float v = red[0][r][lane] + red[1][r][lane] + red[2][r][lane] + red[3][r][lane];
       const int row = b0 + mfma32_row(r, lane);
       part[((size_t)z * batch + row) * FC1_OUT + n0 + i] = v;
+    }
+  } else {
+    if (wave > 0) {
+#pragma unroll
+      for (int r = 0; r < 16; ++r) red[wave - 1][r][lane] = c0[r];
+    }
+    __syncthreads();
+    if (wave == 0) {
+#pragma unroll
+      for (int r = 0; r < 16; ++r) {
+        const float v = c0[r] + red[0][r][lane] + red[1][r][lane] + red[2][r][lane];
+        const int row = b0 + mfma32_row(r, lane);
+        part[((size_t)z * batch + row) * FC1_OUT + n0 + i] = v;
+      }
     }
   }
 }
@@ -294,7 +338,7 @@ __global__ __launch_bounds__(256) void fc_head_train_kernel(
     float base_lr, float lr_decay, float* __restrict__ hd_out, float* __restrict__ dh_out,
     float* __restrict__ dlog_out, float* __restrict__ loss_rows, float* __restrict__ lr_out,
     int* __restrict__ correct, __bf16* __restrict__ dh16, __bf16* __restrict__ dht16,
-    int lbatch) {
+    int lbatch, unsigned long long* __restrict__ prof) {
   // dh16 / dht16 (bf16 engine): the K-packed MFMA operands of fc1 dX / dW1
   // lbatch: the logical batch (schedule, 1 / B); `batch` rows are computed and
   // strided.  Rows >= lbatch are pad rows: this is the one point where the
@@ -302,6 +346,7 @@ __global__ __launch_bounds__(256) void fc_head_train_kernel(
   // later kernel sees zero factors for them.
   __shared__ float red[4][NCLS];
   __shared__ float dlog_s[NCLS];
+  FcStamp stamp(prof, blockIdx.x);
   const int row = blockIdx.x;
   const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
   const long long step = step_ptr ? *step_ptr : 0;
@@ -388,6 +433,171 @@ __global__ __launch_bounds__(256) void fc_head_train_kernel(
       dh16[((j >> 4) * batch + row) * 16 + (j & 15)] = (__bf16)d;
       dht16[((row >> 4) * FC1_OUT + j) * 16 + (row & 15)] = (__bf16)d;
     }
+  }
+}
+
+// The same head with the serial parts taken off the path from the slab loads
+// to dh (set_fc_chain bit 0; same arguments, same outputs):
+//  * every load that does not need the step counter (slabs, w4, biases) is
+//    issued before anything waits on the counter; the counter -> batch offset
+//    -> label chain runs beside them;
+//  * the learning rate (a 64-bit division and a powf on one lane) is formed
+//    by one extra block of the grid, not by wave 0 of block 0 between the
+//    barriers (in a wave of block 0 under the slab loads it still made that
+//    block the last to end);
+//  * the 10 logit sums go through one LDS transpose: every thread leaves its
+//    10 partials, 40 lanes of wave 0 sum 64 each (float4 reads) and meet over
+//    4 lanes, instead of 10 six-step cross-lane chains a wave;
+//  * the 40 lanes gather the 10 logits with independent cross-lane reads and
+//    each forms max, sum and its class's dlogit itself (no butterfly max /
+//    sum chains); loss and `correct` follow the dh stores.
+// Every sum keeps the older kernel's association (wave_sum's butterfly tree,
+// then the waves in order) and every quotient its form, so all outputs are
+// the older kernel's bit for bit.
+// one (class, wave) segment of partials: 64 + 4 floats, so the 4 float4
+// readers of a class start on different banks
+constexpr int HEAD_LD = 68;
+
+template <int NS>
+__global__ __launch_bounds__(256) void fc_head_train2_kernel(
+    const float* __restrict__ part, const float* __restrict__ b3, const float* __restrict__ w4,
+    const float* __restrict__ b4, const int* __restrict__ labels, int n_local,
+    const long long* __restrict__ step_ptr, int batch, float keep_prob, uint32_t seed,
+    uint32_t rank, float base_lr, float lr_decay, float* __restrict__ hd_out,
+    float* __restrict__ dh_out, float* __restrict__ dlog_out, float* __restrict__ loss_rows,
+    float* __restrict__ lr_out, int* __restrict__ correct, __bf16* __restrict__ dh16,
+    __bf16* __restrict__ dht16, int lbatch, unsigned long long* __restrict__ prof) {
+  // step_ptr is __restrict__ (the SGD launch bumps the counter, never this
+  // one), so the counter and the label come through scalar loads: a vector
+  // load of the counter is waited for (vmcnt(0)) ahead of every slab load
+  __shared__ __attribute__((aligned(16))) float sp[NCLS * 4 * HEAD_LD];
+  __shared__ __attribute__((aligned(16))) float dlog_s[12];
+  FcStamp stamp(prof, blockIdx.x);
+  const int row = blockIdx.x;
+  const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
+  const long long step = step_ptr ? *step_ptr : 0;
+  if (row == batch) {  // the extra block (lr_out set): the learning rate, on nobody's path
+    const float e2 = (float)((step * logical_batch(lbatch, batch)) / n_local);
+    if (tid == 0) lr_out[0] = base_lr * powf(lr_decay, e2);
+    return;
+  }
+  float ps[2][NS];
+#pragma unroll
+  for (int u = 0; u < 2; ++u)
+#pragma unroll
+    for (int q = 0; q < NS; ++q)
+      ps[u][q] = part[((size_t)q * batch + row) * FC1_OUT + tid + 256 * u];
+  float w4r[2][NCLS];
+#pragma unroll
+  for (int u = 0; u < 2; ++u)
+#pragma unroll
+    for (int c = 0; c < NCLS; ++c) w4r[u][c] = w4[(tid + 256 * u) * NCLS + c];
+  const float b3v[2] = {b3[tid], b3[tid + 256]};
+  const float b4l = b4[min(lane >> 2, NCLS - 1)];
+  // everything above is in flight before the first wait on the step counter
+  __builtin_amdgcn_sched_barrier(0);
+  const int lb = logical_batch(lbatch, batch);
+  const bool valid = row < lb;
+  const long long off = step_ptr ? (step * lb) % (long long)(n_local - lb) : 0;
+  const int label = labels[off + row];
+  const uint32_t key = dropout_key(seed, rank, (uint32_t)step, 0u);
+  const float scale = 1.f / keep_prob;
+  float z[2], hd[2];
+  bool kp[2];
+  float lg[NCLS];
+#pragma unroll
+  for (int c = 0; c < NCLS; ++c) lg[c] = 0.f;
+#pragma unroll
+  for (int u = 0; u < 2; ++u) {
+    const int j = tid + 256 * u;
+    float s = b3v[u];
+#pragma unroll
+    for (int q = 0; q < NS; ++q) s += ps[u][q];
+    z[u] = s;
+    const float h = fmaxf(s, 0.f);
+    kp[u] = dropout_keep(key, (uint32_t)(row * FC1_OUT + j), keep_prob);
+    hd[u] = kp[u] ? h * scale : 0.f;
+#pragma unroll
+    for (int c = 0; c < NCLS; ++c) lg[c] += hd[u] * w4r[u][c];
+  }
+#pragma unroll
+  for (int c = 0; c < NCLS; ++c) sp[(c * 4 + wv) * HEAD_LD + lane] = lg[c];
+  __syncthreads();
+  float mx = 0.f, se = 1.f, lab_logit = 0.f;  // thread 0 keeps them for the loss
+  int am = 0;
+  if (tid < 4 * NCLS) {  // lane = 4 class + wave segment
+    const float4* seg = reinterpret_cast<const float4*>(sp + tid * HEAD_LD);
+    float4 t[16];
+#pragma unroll
+    for (int i = 0; i < 16; ++i) t[i] = seg[i];
+    __builtin_amdgcn_sched_barrier(0);  // all 16 reads in flight, not pairs
+    // the tree of wave_sum's butterfly (partners 32, 16, 8, 4, 2, 1 lanes
+    // apart), so the wave sums carry the older kernel's bits
+    auto add4 = [](float4 a, float4 b) {
+      return make_float4(a.x + b.x, a.y + b.y, a.z + b.z, a.w + b.w);
+    };
+#pragma unroll
+    for (int w = 8; w > 0; w >>= 1)
+#pragma unroll
+      for (int i = 0; i < w; ++i) t[i] = add4(t[i], t[i + w]);
+    const float v = (t[0].x + t[0].z) + (t[0].y + t[0].w);
+    // the four wave sums of the class, added in wave order as before
+    const int l0 = tid & ~3;
+    const float r0 = __shfl(v, l0, 64), r1 = __shfl(v, l0 + 1, 64);
+    const float r2 = __shfl(v, l0 + 2, 64), r3 = __shfl(v, l0 + 3, 64);
+    // every lane of the section gathers the 10 logits and forms the softmax
+    // (a handful of cross-lane reads, all in flight); one lane a class owns
+    // its dlogit: two quotients a lane here, none in the other waves
+    const float logit = r0 + r1 + r2 + r3 + b4l;
+    float lgt[NCLS];
+#pragma unroll
+    for (int c = 0; c < NCLS; ++c) lgt[c] = __shfl(logit, 4 * c, 64);
+    mx = lgt[0];
+#pragma unroll
+    for (int c = 1; c < NCLS; ++c) {
+      if (lgt[c] > mx) {  // strict: the first maximum wins
+        mx = lgt[c];
+        am = c;
+      }
+    }
+    float e[NCLS];
+#pragma unroll
+    for (int c = 0; c < NCLS; ++c) e[c] = __expf(lgt[c] - mx);
+    // wave_sum's tree over lanes 0..9 (the other lanes held zeros): the older
+    // kernel's sum bit for bit
+    static_assert(NCLS == 10, "softmax sum tree");
+    se = (((e[0] + e[8]) + e[4]) + (e[2] + e[6])) + (((e[1] + e[9]) + e[5]) + (e[3] + e[7]));
+    const int cls = tid >> 2;
+    const float p = __expf(logit - mx) / se;
+    const float dlv = valid ? (p - (cls == label ? 1.f : 0.f)) / (float)lb : 0.f;
+    if ((tid & 3) == 0) {
+      dlog_s[cls] = dlv;
+      dlog_out[row * NCLS + cls] = dlv;
+    }
+#pragma unroll
+    for (int c = 0; c < NCLS; ++c) lab_logit = c == label ? lgt[c] : lab_logit;
+  }
+  __syncthreads();
+  float dl[NCLS];
+#pragma unroll
+  for (int c = 0; c < NCLS; ++c) dl[c] = dlog_s[c];
+#pragma unroll
+  for (int u = 0; u < 2; ++u) {
+    const int j = tid + 256 * u;
+    float d = 0.f;
+#pragma unroll
+    for (int c = 0; c < NCLS; ++c) d += dl[c] * w4r[u][c];
+    d = (kp[u] && z[u] > 0.f) ? d * scale : 0.f;  // pad row: dl == 0, so d == +0.f
+    hd_out[row * FC1_OUT + j] = hd[u];
+    dh_out[row * FC1_OUT + j] = d;
+    if (dh16) {  // K-packed layouts of mnist_bf16.h
+      dh16[((j >> 4) * batch + row) * 16 + (j & 15)] = (__bf16)d;
+      dht16[((row >> 4) * FC1_OUT + j) * 16 + (row & 15)] = (__bf16)d;
+    }
+  }
+  if (tid == 0) {
+    loss_rows[row] = valid ? (logf(se) + mx) - lab_logit : 0.f;  // logsumexp - logit[label]
+    if (correct && valid) atomicAdd(correct, am == label ? 1 : 0);
   }
 }
 
@@ -651,12 +861,13 @@ __device__ __forceinline__ void fc1_dw_sgd(const FcSgd& a, int L, int tid) {
   apply(c1, n0 + 32 + r);
 }
 
+template <bool PROF>  // labs: block stamps into prof; off, the stamp folds away entirely
 __global__ __launch_bounds__(256) void fc1_bwd_kernel(
     const float* __restrict__ a2, const uint8_t* __restrict__ idx2, const float* __restrict__ dh,
     const float* __restrict__ hd, const float* __restrict__ dlog, const float* __restrict__ w1,
     int batch, float* __restrict__ g_w3, float* __restrict__ g_b3, float* __restrict__ g_w4,
     float* __restrict__ g_b4, float* __restrict__ dy2, float* __restrict__ dy2t,
-    float* __restrict__ dp2, int roles) {
+    float* __restrict__ dp2, int roles, unsigned long long* __restrict__ prof) {
   // dy2: NHWC [n][14][14][64]; dy2t: channel-major, zero-bordered
   // [n][64][18][MNIST32_T_LD] (its border is never written); dy2 == nullptr:
   // the compact dp2 [n][7][7][64] instead (fc1_bwd_dx)
@@ -667,6 +878,7 @@ __global__ __launch_bounds__(256) void fc1_bwd_kernel(
   const int n_dx = (roles & 1) ? (batch / 32) * (FC1_IN / 32) : 0;
   const int n_dw = (roles & 2) ? FC1BWD_DW_BLOCKS : 0;
   const int L = xcd_remap(blockIdx.x, gridDim.x);
+  FcStamp stamp(PROF ? prof : nullptr, L);  // by logical block: the roles in grid order
   if (L < n_dx)
     fc1_bwd_dx(L, a2, idx2, dh, w1, batch, dy2, dy2t, dp2, smem);
   else if (L < n_dx + n_dw)
@@ -2579,19 +2791,35 @@ void launch_conv2_fwd_wino(const float* a1, int batch, const float* w2, const fl
 int fc1_train_splits() { return FC1_SPLITS; }
 int fc1_train_t_splits() { return FC1T_SPLITS; }
 
+// labs / A-B (mnist.h): stamps of the FC launches, and which of the shorter
+// forms they run
+static unsigned long long* g_fc_prof = nullptr;
+static int g_fc_chain = FC_CHAIN_DEFAULT;
+void set_fc_prof(unsigned long long* p) { g_fc_prof = p; }
+void set_fc_chain(int mask) { g_fc_chain = mask < 0 ? FC_CHAIN_DEFAULT : mask; }
+int fc_chain() { return g_fc_chain; }
+static unsigned long long* fc_prof(int launch) {
+  return g_fc_prof ? g_fc_prof + (size_t)launch * 2 * FC_PROF_SLOTS : nullptr;
+}
+
 void launch_fc1_fwd_train(const float* a2, const float* w, int batch, float* part,
                           hipStream_t s) {
   // 64x32 tiles, 2-way in-block K split, 14 split-K slabs of 224 (7 K tiles)
   const int kchunk = FC1_IN / FC1_SPLITS;
   dim3 grid(cdiv(batch, 64) * (FC1_OUT / 32), FC1_SPLITS);
-  fc1_fwd_kernel<2, 1, 2, 32, false, FC1_IN / FC1_SPLITS / 32>
-      <<<grid, 256, 0, s>>>(a2, w, nullptr, part, batch, kchunk, 0u, 1.f);
+  if (fc_prof(0))
+    fc1_fwd_kernel<2, 1, 2, 32, false, FC1_IN / FC1_SPLITS / 32, true>
+        <<<grid, 256, 0, s>>>(a2, w, nullptr, part, batch, kchunk, 0u, 1.f, fc_prof(0));
+  else
+    fc1_fwd_kernel<2, 1, 2, 32, false, FC1_IN / FC1_SPLITS / 32>
+        <<<grid, 256, 0, s>>>(a2, w, nullptr, part, batch, kchunk, 0u, 1.f, nullptr);
 }
 
 void launch_fc1_fwd_eval(const float* a2, const float* w, const float* b, int M, float* h,
                          uint32_t key, float keep_prob, hipStream_t s) {
   dim3 grid(cdiv(M, 64) * (FC1_OUT / 64), 1);
-  fc1_fwd_kernel<2, 2, 1, 64, true><<<grid, 256, 0, s>>>(a2, w, b, h, M, FC1_IN, key, keep_prob);
+  fc1_fwd_kernel<2, 2, 1, 64, true>
+      <<<grid, 256, 0, s>>>(a2, w, b, h, M, FC1_IN, key, keep_prob, nullptr);
 }
 
 void launch_fc_head_train(const float* part, const float* b3, const float* w4, const float* b4,
@@ -2601,16 +2829,21 @@ void launch_fc_head_train(const float* part, const float* b3, const float* w4, c
                           float* lr_out, int* correct, hipStream_t s, uint16_t* dh16,
                           uint16_t* dht16, int splits, int lbatch) {
   if (lbatch < 0 || lbatch > batch) throw std::runtime_error("fc_head_train: lbatch > batch");
-#define HEAD(NS_)                                                                              \
-  fc_head_train_kernel<NS_><<<batch, 256, 0, s>>>(part, b3, w4, b4, labels, n_local, step, batch, \
-                                                  keep_prob, seed, rank, base_lr, lr_decay, hd, dh, \
-                                                  dlog, loss_rows, lr_out, correct,              \
-                                                  reinterpret_cast<__bf16*>(dh16),               \
-                                                  reinterpret_cast<__bf16*>(dht16), lbatch)
-  if (splits == FC1T_SPLITS)
-    HEAD(FC1T_SPLITS);
+#define HEAD(K_, NS_, GRID_)                                                                   \
+  K_<NS_><<<GRID_, 256, 0, s>>>(part, b3, w4, b4, labels, n_local, step, batch, keep_prob, seed, \
+                                rank, base_lr, lr_decay, hd, dh, dlog, loss_rows, lr_out, correct, \
+                                reinterpret_cast<__bf16*>(dh16), reinterpret_cast<__bf16*>(dht16), \
+                                lbatch, fc_prof(1))
+  const bool v2 = g_fc_chain & FC_CHAIN_HEAD;
+  const int grid2 = batch + (lr_out ? 1 : 0);  // fc_head_train2_kernel: + its lr block
+  if (splits == FC1T_SPLITS && v2)
+    HEAD(fc_head_train2_kernel, FC1T_SPLITS, grid2);
+  else if (splits == FC1T_SPLITS)
+    HEAD(fc_head_train_kernel, FC1T_SPLITS, batch);
+  else if (splits == FC1_SPLITS && v2)
+    HEAD(fc_head_train2_kernel, FC1_SPLITS, grid2);
   else if (splits == FC1_SPLITS)
-    HEAD(FC1_SPLITS);
+    HEAD(fc_head_train_kernel, FC1_SPLITS, batch);
   else
     throw std::runtime_error("fc_head_train: unsupported slab count");
 #undef HEAD
@@ -2619,8 +2852,19 @@ void launch_fc_head_train(const float* part, const float* b3, const float* w4, c
 void launch_fc1_fwd_train_t(const float* a2t, const float* w, int batch, float* part,
                             hipStream_t s) {
   if (batch <= 0 || batch % 32) throw std::runtime_error("fc1_fwd_t: batch % 32 != 0");
-  fc1_fwd_t_kernel<<<dim3((FC1_OUT / 32) * (batch / 32), FC1T_SPLITS), 256, 0, s>>>(a2t, w, batch,
-                                                                                   part);
+  const dim3 grid((FC1_OUT / 32) * (batch / 32), FC1T_SPLITS);
+#define FWD_T(SPREAD_, UPFRONT_) \
+  fc1_fwd_t_kernel<SPREAD_, UPFRONT_><<<grid, 256, 0, s>>>(a2t, w, batch, part, fc_prof(0))
+  const bool spread = g_fc_chain & FC_CHAIN_FWD, upfront = g_fc_chain & FC_CHAIN_FWD_LOADS;
+  if (spread && upfront)
+    FWD_T(true, true);
+  else if (spread)
+    FWD_T(true, false);
+  else if (upfront)
+    FWD_T(false, true);
+  else
+    FWD_T(false, false);
+#undef FWD_T
 }
 
 void launch_fc_head_eval(const float* h, const float* w4, const float* b4, const int* labels,
@@ -2637,8 +2881,12 @@ void launch_fc1_bwd(const float* a2, const uint8_t* idx2, const float* dh, const
   if (roles <= 0 || roles > 7) throw std::runtime_error("fc1_bwd: roles must be a mask in 1..7");
   const int grid = ((roles & 1) ? (batch / 32) * (FC1_IN / 32) : 0) +
                    ((roles & 2) ? FC1BWD_DW_BLOCKS : 0) + ((roles & 4) ? SMALL_BLOCKS : 0);
-  fc1_bwd_kernel<<<grid, 256, 0, s>>>(a2, idx2, dh, hd, dlog, w1, batch, g_w3, g_b3, g_w4, g_b4,
-                                      dy2, dy2t, dp2, roles);
+  if (fc_prof(2))
+    fc1_bwd_kernel<true><<<grid, 256, 0, s>>>(a2, idx2, dh, hd, dlog, w1, batch, g_w3, g_b3, g_w4,
+                                              g_b4, dy2, dy2t, dp2, roles, fc_prof(2));
+  else
+    fc1_bwd_kernel<false><<<grid, 256, 0, s>>>(a2, idx2, dh, hd, dlog, w1, batch, g_w3, g_b3, g_w4,
+                                               g_b4, dy2, dy2t, dp2, roles, nullptr);
 }
 
 void launch_fc1_bwd_weights(const float* a2, const float* dh, const float* hd, const float* dlog,
