@@ -88,6 +88,8 @@ AUGMENT_FILL = {"mnist_cnn": -0.5, "lenet5": 0.0, "resnet18": 0.0}
 # flip is already 98 forwards per row)
 PREDICT_SPLITS = ("test", "val")
 MAX_TTA_SHIFT = 3
+# --predict-weights: the trained weights, or their moving average (--ema)
+PREDICT_WEIGHTS = ("raw", "ema")
 
 
 def parse_augment(spec: str, model: str = "mnist_cnn"):
@@ -120,6 +122,39 @@ def parse_augment(spec: str, model: str = "mnist_cnn"):
     if "shift" not in seen and "flip" not in seen:
         raise ValueError(f"augment spec {spec!r} asks for neither a shift nor a flip")
     return K, "flip" in seen, float(seen.get("fill", AUGMENT_FILL.get(model, 0.0)))
+
+
+def parse_ema(spec: str):
+    """`DECAY` (a float, 0 < DECAY < 1) and optionally `every:K` (K >= 1), comma
+    separated, in any order, each at most once -> (decay, K); K = 1 without
+    an `every` (the definition: docs/ACCURACY.md)."""
+    if not isinstance(spec, str) or not spec.strip():
+        raise ValueError("empty ema spec; expected e.g. '0.999', '0.99,every:4'")
+    seen = {}
+    for item in spec.split(","):
+        name, sep, val = item.strip().partition(":")
+        key = "every" if sep else "decay"
+        try:
+            if sep and name == "every":
+                v = int(val)
+            elif not sep:
+                v = float(name)
+            else:
+                raise ValueError
+        except ValueError:
+            raise ValueError(f"bad item {item!r} in ema spec {spec!r}; expected DECAY or "
+                             f"every:K") from None
+        if key in seen:
+            raise ValueError(f"ema spec {spec!r} names {key!r} twice")
+        seen[key] = v
+    if "decay" not in seen:
+        raise ValueError(f"ema spec {spec!r} names no decay")
+    decay, K = seen["decay"], seen.get("every", 1)
+    if not 0.0 < decay < 1.0:  # (false for nan)
+        raise ValueError(f"ema decay must be in (0, 1), got {decay}")
+    if K < 1:
+        raise ValueError(f"ema every must be at least 1, got {K}")
+    return float(decay), int(K)
 
 
 @dataclasses.dataclass
@@ -183,6 +218,10 @@ class TrainConfig:
     # for every row and pass on the device (parse_augment, runtime/shuffle.py);
     # None = every pass shows the same pixels
     augment: Optional[str] = None
+    # exponential moving average of the weights, updated on the device after
+    # every K-th step (parse_ema: DECAY[,every:K]), evaluated at every logged
+    # eval event, saved with the checkpoints; None = no average is kept
+    ema: Optional[str] = None
     # learning rate / optimiser
     base_lr: float = BASE_LR
     lr_decay: float = LR_DECAY
@@ -218,6 +257,9 @@ class TrainConfig:
     predict_topk: int = 3
     predict_tta: Optional[str] = None  # test-time augmentation views, parse_augment syntax
     predict_probs: bool = False
+    # raw | ema: the checkpoint's trained weights or their moving average (--ema);
+    # None = raw, not named (the JSON record then has no "weights" entry)
+    predict_weights: Optional[str] = None
     quiet: bool = False
     # robustness: process-group / collective timeout (a dead rank turns into
     # an error instead of a hang) and a cross-replica consistency probe at
@@ -260,6 +302,15 @@ class TrainConfig:
             raise ValueError("dropout_keep must be in (0, 1]")
         if self.augment is not None:
             parse_augment(self.augment, self.model)
+        if self.ema is not None:
+            parse_ema(self.ema)
+            if self.model == "resnet18":
+                raise ValueError("--ema does not support --model resnet18 (its forward lives in "
+                                 "the autograd engine, and its BatchNorm statistics would need "
+                                 "averaging too); use mnist_cnn or lenet5")
+        if self.predict_weights is not None and self.predict_weights not in PREDICT_WEIGHTS:
+            raise ValueError(f"unknown predict weights {self.predict_weights!r}; choose from "
+                             f"{PREDICT_WEIGHTS}")
         if self.ckpt_best:
             if self.model != "mnist_cnn":
                 raise ValueError(f"--ckpt-best selects on the validation split, and the "
@@ -272,6 +323,8 @@ class TrainConfig:
         elif (self.predict_labels or self.predict_out or self.predict_tta or self.predict_probs):
             raise ValueError("--predict-labels / --predict-out / --predict-tta / --predict-probs "
                              "need --predict SRC")
+        elif self.predict_weights is not None:
+            raise ValueError("--predict-weights needs --predict SRC")
         return self
 
     def _validate_predict(self) -> None:
@@ -371,6 +424,11 @@ def build_arg_parser(prog: str = "mpipy.py") -> argparse.ArgumentParser:
                    help="random shift and / or horizontal flip of every training image, redrawn "
                         "each pass on the device: shift:K[,flip][,fill:V] or flip (fill: the value "
                         "shifted in, default -0.5 for mnist_cnn, 0 otherwise)")
+    p.add_argument("--ema", default=d.ema, metavar="SPEC",
+                   help="keep an exponential moving average of the weights on the device: "
+                        "DECAY[,every:K] (0 < DECAY < 1, updated after every K-th step with TF's "
+                        "num_updates warm-up); evaluated at every logged eval event, saved with "
+                        "the checkpoints (mnist_cnn, lenet5)")
     p.add_argument("--base-lr", type=float, default=d.base_lr)
     p.add_argument("--lr-decay", type=float, default=d.lr_decay)
     p.add_argument("--momentum", type=float, default=d.momentum)
@@ -392,7 +450,8 @@ def build_arg_parser(prog: str = "mpipy.py") -> argparse.ArgumentParser:
                         "(one extra log line on rank 0, extra keys in --metrics-jsonl)")
     p.add_argument("--ckpt-best", default=None, metavar="PATH",
                    help="write the checkpoint there whenever the global validation error "
-                        "improves (implies --eval-metrics; mnist_cnn, --eval-every > 0)")
+                        "improves (implies --eval-metrics; mnist_cnn, --eval-every > 0); "
+                        "with --ema the selection stays on the raw weights")
     p.add_argument("--predict", default=None, metavar="SRC",
                    help="no training: classify SRC with the checkpoint --resume. SRC: an IDX "
                         "ubyte image file (raw or gzip), a .npy of uint8 or float32 rows, or "
@@ -408,6 +467,10 @@ def build_arg_parser(prog: str = "mpipy.py") -> argparse.ArgumentParser:
                         "shift:K[,flip][,fill:V] (K <= 3; (2K+1)^2 views, twice with flip)")
     p.add_argument("--predict-probs", action="store_true",
                    help="--predict-out also holds the class probabilities [n, 10]")
+    p.add_argument("--predict-weights", default=d.predict_weights, choices=PREDICT_WEIGHTS,
+                   help="predict with the checkpoint's trained weights (raw, the default) or with "
+                        "their moving average (ema: a checkpoint of an --ema run); when given, "
+                        "the JSON record names it under \"weights\"")
     p.add_argument("--quiet", action="store_true")
     p.add_argument("--collective-timeout-s", type=float, default=d.collective_timeout_s,
                    help="process-group / collective timeout (seconds)")

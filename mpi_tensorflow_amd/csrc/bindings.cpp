@@ -12,6 +12,7 @@
 
 #include "idx_loader.h"
 #include "kernels/augment.h"
+#include "kernels/ema.h"
 #include "kernels/mnist.h"
 #include "kernels/mnist_bf16.h"
 #include "kernels/ops_generic.h"
@@ -447,6 +448,12 @@ PYBIND11_MODULE(_C, m) {
   });
   o.def("scale", [](uintptr_t x, long long n, float a, uintptr_t s) {
     optim::launch_scale(P<float>(x), n, a, S(s));
+    check_launch();
+  });
+  o.def("ema_update", [](uintptr_t ema, uintptr_t w, long long n, float decay, long long K,
+                         uintptr_t step_ptr, long long step_const, uintptr_t s) {
+    optim::launch_ema(P<float>(ema), P<const float>(w), n, decay, K, P<const long long>(step_ptr),
+                      step_const, S(s));
     check_launch();
   });
 

@@ -807,6 +807,62 @@ def softmax(logits: torch.Tensor) -> torch.Tensor:
     return y
 
 
+# ------------------------------------------------- weight averaging (--ema) --
+def ema_decay(step: int, decay: float, K: int = 1) -> Optional[float]:
+    """The decay `d` of the update after optimizer step `step` (TF's
+    num_updates warm-up, in float32 arithmetic as the kernel computes it), or
+    None when that step updates nothing (step % K != 0)."""
+    import numpy as np
+
+    t, K = int(step), int(K)
+    if K < 1:
+        raise ValueError(f"ema: K must be at least 1, got {K}")
+    if t % K != 0:
+        return None
+    u = np.float32(t // K - 1)  # earlier updates
+    d = (np.float32(1) + u) / (np.float32(10) + u)
+    return float(min(np.float32(decay), d))
+
+
+def ema_update(ema: torch.Tensor, w: torch.Tensor, step, decay: float, K: int = 1) -> torch.Tensor:
+    """One update of the moving average `ema` of the flat fp32 buffer `w`, in
+    place (config.parse_ema has the spec, docs/ACCURACY.md the definition):
+    with t = `step`, the number of optimizer steps applied, nothing when
+    t % K != 0, else d = min(decay, (1 + u) / (10 + u)) with u = t / K - 1
+    in float32 and ema = fma(1 - d, w - ema, ema) per element.
+
+    step: an int, or a one-element int64 tensor (on the GPU: the device step
+    counter, read by the kernel - nothing is copied back, so the call can be
+    captured into a graph).  Native kernel on the GPU (ema.hip) on the current
+    stream; torch on the CPU oracle path, where the fma is the exact float64
+    product and sum rounded to float32 (it differs from the kernel's single
+    rounding only where the float64 sum lands on a float32 rounding tie)."""
+    import numpy as np
+
+    if (ema.dtype != torch.float32 or w.dtype != torch.float32 or ema.dim() != 1
+            or ema.shape != w.shape or ema.device != w.device
+            or not (ema.is_contiguous() and w.is_contiguous())):
+        raise ValueError("ema_update takes two contiguous flat fp32 buffers of one size and device")
+    if ema.is_cuda and not _ORACLE:
+        if isinstance(step, torch.Tensor):
+            if step.dtype != torch.int64 or step.numel() != 1 or step.device != ema.device:
+                raise ValueError("ema_update: a device step must be one int64 on the buffers' device")
+            sp, sc = ptr(step), 0
+        else:
+            sp, sc = 0, int(step)
+        native().optim.ema_update(ptr(ema), ptr(w.detach()), ema.numel(), float(decay), int(K), sp, sc,
+                                  stream_handle())
+        return ema
+    d = ema_decay(int(step.item()) if isinstance(step, torch.Tensor) else int(step), decay, K)
+    if d is None:
+        return ema
+    omd = float(np.float32(1) - np.float32(d))
+    with torch.no_grad():
+        diff = (w.detach() - ema).double()  # the fp32 difference, then exact in fp64
+        ema.copy_((omd * diff + ema.double()).float())
+    return ema
+
+
 # ------------------------------------------------------- evaluation metrics --
 class EvalMetricsOut:
     """The accumulators of one evaluation, owned by the caller: pass it as

@@ -5,7 +5,8 @@ generic_engine.py).
   param / grad / momentum buffers in the parallel/flat.py layout (allocated by
   the engine: `params`, `grads`, `mom`, `layout`), the host step counter, the
   reference's LR schedule and batch offset (step * B) % (N_local - B), DP by
-  per-step gradient all-reduce (`grad_sync`).
+  per-step gradient all-reduce (`grad_sync`); under cfg.ema one more flat
+  buffer `ema`, the moving average of `params` (`init_ema`, `ema_step`).
 * `GraphStepDriver`: `train` / `capture` / `_run_steps` of the engines whose
   step is a fixed launch sequence replayed from captured G-step graphs; the
   engine supplies `_launch_one()` and `_graph(n)`.
@@ -23,6 +24,7 @@ from typing import Dict, Iterator, List, Optional
 import torch
 
 from .. import config as C
+from ..ops import functional as Fn
 from ..parallel import dist as D
 from ..parallel.comm import DeviceComm
 from ..parallel.sync import replicas_identical
@@ -48,6 +50,26 @@ class EngineBase:
         # force_sync: exercise the collective path at world 1
         self.grad_sync = comm is not None and (force_sync or (cfg.sync == "grad" and world > 1))
         self.shuffler = None  # cfg.shuffle / cfg.augment: the per-pass rows (runtime/shuffle.py)
+        # cfg.ema: the moving average of `params` (same layout; init_ema), else None
+        self.ema: Optional[torch.Tensor] = None
+        self.ema_decay, self.ema_every = C.parse_ema(cfg.ema) if cfg.ema is not None else (0.0, 1)
+
+    def init_ema(self) -> None:
+        """cfg.ema: allocates `ema` next to the (initialised) params and sets
+        it to them - TF's shadow-variable initial value.  Without the flag
+        nothing is allocated."""
+        if self.cfg.ema is None:
+            return
+        if self.layout.total % 4:
+            raise ValueError(f"--ema needs a flat buffer of 4k floats, got {self.layout.total}")
+        self.ema = self.params.detach().clone()
+
+    def ema_step(self, step=None) -> None:
+        """One moving-average update on the current stream, after a step's
+        SGD: `step` = the optimizer steps applied (default: the device
+        counter, which the SGD has incremented; no host read)."""
+        Fn.ema_update(self.ema, self.params, self.step_dev if step is None else step,
+                      self.ema_decay, self.ema_every)
 
     def param_views(self) -> Dict[str, torch.Tensor]:
         return self.layout.views(self.params)

@@ -82,6 +82,10 @@ class GenericEngine(EngineBase):
         self.train_x = torch.from_numpy(np.ascontiguousarray(train_x, np.float32)).to(device)
         self.train_y = torch.from_numpy(np.asarray(train_y).astype(np.int32)).to(device)
         self.on_gpu = device.type == "cuda" and not self.oracle
+        if cfg.ema is not None and self.on_gpu:
+            raise ValueError(f"--ema: the op-by-op GPU engine keeps no average (model {cfg.model}); "
+                             "mnist_cnn and lenet5 run their own engines on a GPU")
+        self.init_ema()
         self.wcache = None
         self.use_graph = cfg.graph and self.on_gpu
         self.graph_steps = max(1, cfg.graph_steps)
@@ -454,6 +458,8 @@ class GenericEngine(EngineBase):
                 for _ in range(k):
                     self._step_cpu()
                     self.step += 1
+                    if self.ema is not None:
+                        self.ema_step(self.step)
             return
         if self.wcache is not None:
             # the weights may have changed since the last step (init, checkpoint,

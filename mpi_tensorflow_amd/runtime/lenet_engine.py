@@ -62,6 +62,7 @@ class NativeLenetEngine(GraphStepDriver, EngineBase):
         self.model.init_params(host, cfg.seed)
         dev = device
         self.params = host.to(dev)
+        self.init_ema()
         self.grads = torch.zeros(self.layout.total, device=dev)
         self.mom = torch.zeros(self.layout.total, device=dev)
         self.bn: Dict = {}
@@ -184,6 +185,8 @@ class NativeLenetEngine(GraphStepDriver, EngineBase):
     # ------------------------------------------------------------------ step
     def _launch_one(self) -> None:
         self.exe.train_step(stream_handle(), self._sync)
+        if self.ema is not None:  # (one stream: the step's parameter writes are in order)
+            self.ema_step()
 
     def _set_sync(self, c, mode: Optional[str] = None) -> None:
         mode = self.xgmi_mode if mode is None else mode
@@ -225,7 +228,8 @@ class NativeLenetEngine(GraphStepDriver, EngineBase):
         G = self.graph_steps
         if self.shuffler is not None:  # the (discarded) trial steps read the current pass
             self.shuffler.ensure(self.step)
-        snap = StateSnapshot(self.params, self.mom, self.step_dev)
+        snap = StateSnapshot(self.params, self.mom, self.step_dev,
+                             *([self.ema] if self.ema is not None else []))
         xh = self.xcomm.native_handle
         base = (self._native_comm, "two-phase")
         cands = [("all-reduce",) + base, ("xgmi", xh, "two-phase"),

@@ -66,6 +66,7 @@ class MnistEngineBase(EngineBase):
         host = torch.zeros(self.layout.total, dtype=torch.float32)
         M.init_params(host, self.layout, seed=cfg.seed)
         self.params.copy_(host)
+        self.init_ema()
         self.drop_seed = cfg.seed
 
     def l2_value(self) -> float:
@@ -122,6 +123,8 @@ class TorchMnistEngine(MnistEngineBase):
             self.mom.mul_(self.cfg.momentum).add_(g)
             self.params.sub_(lr * self.mom)
             self.step += 1
+            if self.ema is not None:
+                self.ema_step(self.step)
 
     def loss_value(self) -> float:
         return self.last_loss + self.l2_value()
@@ -407,6 +410,12 @@ class NativeMnistEngine(GraphStepDriver, MnistEngineBase):
     def _launch_one(self):
         cs = stream_handle(self.comm_stream) if self.comm_stream is not None else 0
         self.exe.train_step(stream_handle(), self._native_comm, cs, self._native_comm2)
+        if self.ema is not None:
+            # the average reads the step's final parameters: under the sharded,
+            # split and defer schedules the FC update finishes on the comm stream
+            # (every other schedule's last parameter write is in stream order)
+            self.exe.join(stream_handle())
+            self.ema_step()
 
     def _graph(self, n: int, sticky: bool = True) -> Optional[torch.cuda.CUDAGraph]:
         """Captured graph of n steps under the current schedule.  A failed
@@ -548,7 +557,8 @@ class NativeMnistEngine(GraphStepDriver, MnistEngineBase):
         # the trial steps take the derived weights (Winograd transforms, bf16
         # shadows) as current: derive them from the weights first
         self.exe.refresh_shadows(stream_handle())
-        return StateSnapshot(self.params, self.mom, self.step_dev)
+        return StateSnapshot(self.params, self.mom, self.step_dev,
+                             *([self.ema] if self.ema is not None else []))
 
     def _xgmi_step_matches(self, sched: int, name: str, snap: StateSnapshot) -> Optional[str]:
         """Collective: one eager step of the xGMI schedule `sched` against one

@@ -105,9 +105,15 @@ class PredictResult:
 
 class Predictor:
     def __init__(self, model: str, params: torch.Tensor, dtype: str = "fp32",
-                 backend: str = "auto", step: int = 0, meta: Optional[Dict[str, str]] = None):
+                 backend: str = "auto", step: int = 0, meta: Optional[Dict[str, str]] = None,
+                 weights: str = "raw"):
         """`params`: the flat fp32 parameter buffer in the model's layout, on
-        the device the predictions run on (used in place)."""
+        the device the predictions run on (used in place).  `weights` names
+        what it holds: the trained weights ("raw") or their moving average
+        ("ema", --ema); the forward is the same."""
+        if weights not in C.PREDICT_WEIGHTS:
+            raise ValueError(f"unknown weights {weights!r}; choose from {C.PREDICT_WEIGHTS}")
+        self.weights = weights
         _check_model(model)
         if dtype not in C.DTYPES:
             raise ValueError(f"unknown dtype {dtype!r}; choose from {C.DTYPES}")
@@ -131,6 +137,7 @@ class Predictor:
         self.classes = C.NUM_CLASSES
         self.bf16 = dtype == "bf16"
         self._ws: Optional[tuple] = None
+        self._eval_out: Optional[tuple] = None
         self._shadows = None
         if backend == "native":
             self._C = native()
@@ -139,10 +146,16 @@ class Predictor:
     # ---------------------------------------------------------- construction
     @classmethod
     def from_checkpoint(cls, path: str, model: Optional[str] = None, dtype: str = "fp32",
-                        device: str = "auto", backend: str = "auto") -> "Predictor":
+                        device: str = "auto", backend: str = "auto",
+                        weights: str = "raw") -> "Predictor":
         """A checkpoint of utils/checkpoint.py, written at any world size (the
         LR schedule and the shards its `world` entry guards do not apply
-        here); momentum slots are not read."""
+        here); momentum slots are not read.  weights="ema": the moving
+        average an --ema run saved (`<name>/ExponentialMovingAverage`)
+        instead of the trained weights."""
+        if weights not in C.PREDICT_WEIGHTS:
+            raise ValueError(f"unknown weights {weights!r}; choose from {C.PREDICT_WEIGHTS}")
+        suffix = ckpt_mod.EMA_SUFFIX if weights == "ema" else ""
         dev = D.resolve_device(device) if not isinstance(device, torch.device) else device
         with np.load(path, allow_pickle=False) as z:
             meta = {k[len(ckpt_mod.META_PREFIX):]: str(z[k]) for k in z.files
@@ -159,28 +172,36 @@ class Predictor:
             host = torch.zeros(layout.total, dtype=torch.float32)
             views = layout.views(host)
             for s in layout.specs:
-                if s.tf_name not in z.files:
-                    raise ValueError(f"{path}: missing {s.tf_name} ({s.name})")
-                w = z[s.tf_name]
+                key = s.tf_name + suffix
+                if key not in z.files:
+                    raise ValueError(f"{path}: missing {key} ({s.name})" + (
+                        "; the checkpoint was written without --ema" if suffix else ""))
+                w = z[key]
                 if tuple(w.shape) != tuple(s.shape):
-                    raise ValueError(f"{path}: {s.tf_name} ({s.name}) has shape {w.shape}, "
+                    raise ValueError(f"{path}: {key} ({s.name}) has shape {w.shape}, "
                                      f"expected {s.shape}")
                 views[s.name].copy_(torch.from_numpy(np.ascontiguousarray(w, np.float32)))
             if ckpt_mod.STEP_META in z.files:
                 step = int(z[ckpt_mod.STEP_META])
             else:
                 step = int(float(z[ckpt_mod.STEP_NAME])) if ckpt_mod.STEP_NAME in z.files else 0
-        return cls(model, host.to(dev), dtype, backend, step, meta)
+        return cls(model, host.to(dev), dtype, backend, step, meta, weights)
 
     @classmethod
-    def from_engine(cls, engine) -> "Predictor":
+    def from_engine(cls, engine, weights: str = "raw") -> "Predictor":
         """Shares the engine's parameter buffer (zero copy): later training
-        steps and in-place writes show in the next predict()."""
+        steps and in-place writes show in the next predict().  weights="ema":
+        the engine's moving average (cfg.ema) instead, shared the same way."""
         cfg = engine.cfg
+        buf = engine.params
+        if weights == "ema":
+            buf = getattr(engine, "ema", None)
+            if buf is None:
+                raise ValueError("the engine keeps no moving average (it was built without --ema)")
         native_kind = str(getattr(engine, "kind", "")).startswith("native")
         dtype = "bf16" if getattr(engine, "bf16", False) and cfg.model == "mnist_cnn" else "fp32"
-        return cls(cfg.model, engine.params, dtype, "native" if native_kind else "torch",
-                   step=getattr(engine, "step", 0), meta={"model": cfg.model})
+        return cls(cfg.model, buf, dtype, "native" if native_kind else "torch",
+                   step=getattr(engine, "step", 0), meta={"model": cfg.model}, weights=weights)
 
     def _make_ptrs(self):
         C_, off = self._C, self.layout.offsets
@@ -318,6 +339,31 @@ class Predictor:
                              topk_prob=out.topk_prob, scores=out.scores, n=n, views=V,
                              seconds=seconds, probs=out.probs if return_probs else None,
                              metrics=mo.result() if mo is not None else None)
+
+    @torch.no_grad()
+    def evaluate(self, x, labels, chunk: int = 2000) -> EvalMetrics:
+        """The metrics of labelled rows, one view (what predict(x, labels=...)
+        reports as `metrics`), for an evaluation that comes round again: the
+        result buffers are kept for the next call with as many rows, so with
+        fp32 rows and int32 labels already on the device a repeated call
+        allocates no device memory."""
+        xd = self._rows(x)
+        n = int(xd.shape[0])
+        yd = self._labels(labels, n)
+        if yd is None:
+            raise ValueError("evaluate needs labels")
+        dev, Cn = self.device, self.classes
+        oracle = self.backend != "native"
+        if self._eval_out is None or self._eval_out[0] != n:
+            out = Fn.PredictHeadOut(torch.empty((n, Cn), device=dev), torch.empty((n, Cn), device=dev),
+                                    torch.empty((n, 1), dtype=torch.int32, device=dev),
+                                    torch.empty((n, 1), device=dev))
+            self._eval_out = (n, out, Fn.EvalMetricsOut(Cn, dev, oracle=oracle))
+        _, out, mo = self._eval_out
+        mo.zero_()
+        run = self._predict_native if self.backend == "native" else self._predict_torch
+        run(xd, yd, [(0, 0, False)], 0.0, 1, min(int(chunk), max(n, 1)), out, mo)
+        return mo.result()
 
     def _sync(self) -> None:
         if self.device.type == "cuda":
@@ -460,7 +506,7 @@ def predict_main(cfg: C.TrainConfig, di: Optional[D.DistInfo] = None) -> Dict:
     di = di or D.init(str(device), timeout_s=cfg.collective_timeout_s)
     rank, world = di.rank, di.world
     pr = Predictor.from_checkpoint(cfg.resume, model=cfg.model, dtype=cfg.dtype, device=device,
-                                   backend=cfg.backend)
+                                   backend=cfg.backend, weights=cfg.predict_weights or "raw")
     n, a, x, y, desc = load_source(cfg, rank, world)
     views = len(tta_views(cfg.predict_tta, cfg.model)[0])
     res = pr.predict(x, topk=cfg.predict_topk, tta=cfg.predict_tta, labels=y,
@@ -482,6 +528,8 @@ def predict_main(cfg: C.TrainConfig, di: Optional[D.DistInfo] = None) -> Dict:
     rec = {"model": pr.model, "dtype": pr.dtype, "n": n, "views": views, "world": world,
            "checkpoint_step": pr.step, "images_per_sec": n / max(seconds, 1e-9),
            "out": cfg.predict_out}
+    if cfg.predict_weights is not None:  # (a record without the flag is what it always was)
+        rec["weights"] = pr.weights
     if metrics is not None:
         rec.update(error=metrics.error, loss=metrics.loss, top3_error=metrics.topk_error(3),
                    confusion=metrics.confusion.tolist())

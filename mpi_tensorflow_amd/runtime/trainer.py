@@ -21,6 +21,7 @@ from __future__ import annotations
 
 import dataclasses
 import time
+import warnings
 from typing import Dict, Optional
 
 import numpy as np
@@ -71,8 +72,12 @@ class RunSummary:
     final_test_loss: Optional[float] = None
     final_val_error: Optional[float] = None
     final_val_loss: Optional[float] = None
+    # --ema only: the final test error of the averaged weights
+    final_ema_test_error_local: Optional[float] = None
+    final_ema_test_error_global: Optional[float] = None
 
-    _OPTIONAL = ("final_test_loss", "final_val_error", "final_val_loss")
+    _OPTIONAL = ("final_test_loss", "final_val_error", "final_val_loss",
+                 "final_ema_test_error_local", "final_ema_test_error_global")
 
     def as_dict(self) -> Dict:
         d = dataclasses.asdict(self)
@@ -111,6 +116,9 @@ class Trainer:
                                     self.engine.mom, extra=self.engine.extra_state(),
                                     expect={"model": cfg.model, "world": self.world})
             self.engine.set_step(step)
+            if self.engine.ema is not None:
+                self._resume_ema(cfg.resume)
+        self._ema_predictor: Dict = {}  # --ema: split -> the Predictor on engine.ema (kept)
         self.metrics = MetricsWriter(cfg.metrics_jsonl, self.rank)
         # the native MNIST engine evaluates device arrays: the test and the
         # validation split are uploaded at their first evaluation and stay
@@ -277,6 +285,64 @@ class Trainer:
             line += f" (best {self.best_val_error:.2f}% at step {self.best_step})"
         return err, rec, line
 
+    def _resume_ema(self, path: str) -> None:
+        """--ema on resume: the checkpoint's average, or - from a checkpoint
+        written without --ema - the loaded parameters, with a warning; a saved
+        spec other than this run's continues the saved average under the new one."""
+        eng = self.engine
+        found, spec = ckpt_mod.load_ema(path, eng.layout, eng.ema)
+        if not found:
+            with torch.no_grad():
+                eng.ema.copy_(eng.params.detach())
+            warnings.warn(f"{path} holds no moving average (written without --ema): the average "
+                          f"starts from the loaded parameters")
+        elif spec is not None and C.parse_ema(spec) != C.parse_ema(self.cfg.ema):
+            warnings.warn(f"{path}: saved ema={spec} but this run has ema={self.cfg.ema}; the saved "
+                          f"average continues under the new spec")
+
+    def _ema_event(self, step: int, with_metrics: bool):
+        """--ema at a logged eval event: the averaged weights on this rank's
+        test split, through a Predictor that shares `engine.ema` (zero copy; the
+        engines' static eval forward, so nothing of training is touched) and is
+        kept with its workspaces for the later events -> (the keys the event
+        adds to its metrics record, rank 0's extra log line).  with_metrics
+        (--eval-metrics): also the test loss and the validation split, summed
+        over the ranks as _metrics_event sums them."""
+        from .predict import Predictor
+
+        splits = ["test"]
+        if with_metrics and self.shard.val_x.shape[0] > 0:  # the same on every rank
+            splits.append("val")
+        parts = {}
+        on_dev = self.device.type == "cuda"
+        for split in splits:
+            # (a Predictor a split: each keeps the result buffers of its row count)
+            if split not in self._ema_predictor:
+                self._ema_predictor[split] = Predictor.from_engine(self.engine, weights="ema")
+            x, y = self._split(split)
+            xd = self.eval_cache[split].get(x, self.device) if on_dev else x
+            parts[split] = self._ema_predictor[split].evaluate(
+                xd, self._labels_dev(split, y) if on_dev else y)
+        err = parts["test"].error
+        rec = {"ema_test_error": err}
+        line = f"[ema] step {step}: test error {err:.2f}%"
+        if with_metrics:
+            packed = [m.pack() for m in parts.values()]
+            ints = np.concatenate([p[0] for p in packed])
+            sums = np.concatenate([p[1] for p in packed])
+            if self.world > 1:
+                with self.watchdog.guard(f"ema evaluation metrics all-reduce at step {step}"):
+                    ints, sums = D.allreduce_sum_host_array(ints), D.allreduce_sum_host_array(sums)
+            k = parts["test"].classes
+            per = k * (k + 1) + 2
+            for i, name in enumerate(parts):
+                parts[name] = EvalMetrics.unpack(ints[i * per:(i + 1) * per], sums[i:i + 1], k)
+            test, val = parts["test"], parts.get("val")
+            rec.update(ema_test_loss=test.loss, ema_test_error_global=test.error)
+            if val is not None:
+                rec.update(ema_val_error=val.error, ema_val_loss=val.loss)
+        return rec, line
+
     def eval_prediction(self, x: np.ndarray, dropout: Optional[bool] = None) -> torch.Tensor:
         """`eval_prediction = softmax(model(eval_data))` of the reference
         (/root/reference/mpipy.py:68): class probabilities [n, 10] (dropout
@@ -314,6 +380,11 @@ class Trainer:
         if not replicas_identical(self.engine.params):
             raise RuntimeError(f"replicas diverged at step {step}: the bitwise weight "
                                f"fingerprints differ between ranks")
+        # the average follows the weights every step: identical only under grad sync
+        if self.engine.ema is not None and self.cfg.sync == "grad" and not averaged:
+            if not replicas_identical(self.engine.ema):
+                raise RuntimeError(f"replicas diverged at step {step}: the bitwise fingerprints of "
+                                   f"the averaged weights (--ema) differ between ranks")
 
     def sync_schedule(self) -> str:
         return getattr(self.engine, "sync_schedule", "n/a")
@@ -370,11 +441,17 @@ class Trainer:
                     err, extra, mline = self._metrics_event(last)
                 else:
                     err = self.evaluate()
+                if eng.ema is not None and logged:
+                    erec, eline = self._ema_event(last, cfg.eval_metrics)
                 eval_t += time.perf_counter() - t1
                 if logged:
                     emit(progress_line(self.rank, last, err), cfg.quiet)
                     if extra and self.rank == 0:
                         emit(mline, cfg.quiet)
+                    if eng.ema is not None:
+                        extra = {**extra, **erec}
+                        if self.rank == 0:
+                            emit(eline, cfg.quiet)
                     self.metrics.write(step=last, test_error=err, loss=eng.loss_value(), **extra,
                                        sync_schedule=self.sync_schedule(),
                                        lr=eng.lr(last), train_seconds=train_t,
@@ -406,10 +483,20 @@ class Trainer:
                 emit(mline, cfg.quiet)
         else:
             final_err = self.evaluate()
+        ema_err = None
+        if eng.ema is not None:
+            erec, eline = self._ema_event(s - 1, cfg.eval_metrics)
+            extra = {**extra, **erec}
+            ema_err = erec["ema_test_error"]
+            if self.rank == 0:
+                emit(eline, cfg.quiet)
         eval_t += time.perf_counter() - t1
         n_test = self.shard.test_x.shape[0]
         wrong_g = D.allreduce_sum_host(final_err * n_test / 100.0)
         n_g = D.allreduce_sum_host(float(n_test))
+        ema_err_g = None
+        if ema_err is not None:
+            ema_err_g = 100.0 * D.allreduce_sum_host(ema_err * n_test / 100.0) / max(n_g, 1)
         train_t_max = D.allreduce_max_host(train_t)
         images = trained * cfg.batch_size
         summary = RunSummary(
@@ -423,7 +510,8 @@ class Trainer:
             comm=getattr(self.comm, "kind", "none"), synthetic=self.shard.synthetic,
             sync_schedule=self.sync_schedule(), xgmi_gate=self.comms.xgmi_status,
             final_test_loss=extra.get("test_loss"), final_val_error=extra.get("val_error"),
-            final_val_loss=extra.get("val_loss"))
+            final_val_loss=extra.get("val_loss"),
+            final_ema_test_error_local=ema_err, final_ema_test_error_global=ema_err_g)
         self.metrics.write(final=True, **summary.as_dict(), **extra)
         if cfg.ckpt:
             self.save_checkpoint(cfg.ckpt)
@@ -441,8 +529,12 @@ class Trainer:
         self._health("before a checkpoint")
         self.engine.sync_optimizer_state()  # sharded FC momentum -> whole buffer
         if self.rank == 0:
-            ckpt_mod.save(path, self.engine.layout, self.engine.params, self.engine.mom,
-                          self.engine.step, meta={"model": self.cfg.model, "world": self.world,
-                                                  "sync_schedule": self.sync_schedule()},
-                          extra=self.engine.extra_state())
+            eng = self.engine
+            meta = {"model": self.cfg.model, "world": self.world,
+                    "sync_schedule": self.sync_schedule()}
+            extra = dict(eng.extra_state())
+            if eng.ema is not None:  # <tf_name>/ExponentialMovingAverage + the spec
+                extra.update(ckpt_mod.ema_arrays(eng.layout, eng.ema))
+                meta[ckpt_mod.EMA_META] = self.cfg.ema
+            ckpt_mod.save(path, eng.layout, eng.params, eng.mom, eng.step, meta=meta, extra=extra)
         D.barrier()

@@ -10,6 +10,7 @@ reference's unnamed variables:
     Variable_2 conv2_weight [5,5,32,64] HWIO      Variable_6 fc2_weight [512,10]
     Variable_3 conv2_bias   [64]                  Variable_7 fc2_bias   [10]
     Variable_8 iter_ (float32 global step)        <name>/Momentum  optimizer slots
+                                                  <name>/ExponentialMovingAverage  (--ema)
 
 Non-trained model state (the BatchNorm running statistics of ResNet-18) is
 stored as extra named arrays under TF's names (`<bn>/moving_mean`,
@@ -37,6 +38,10 @@ from ..parallel.flat import FlatLayout
 STEP_NAME = "Variable_8"
 META_PREFIX = "__meta__/"
 STEP_META = META_PREFIX + "step"
+# --ema: the moving average of every parameter, under the name TF1's
+# tf.train.ExponentialMovingAverage gives a variable's shadow, and the spec
+EMA_SUFFIX = "/ExponentialMovingAverage"
+EMA_META = "ema"
 
 
 def to_arrays(layout: FlatLayout, params: torch.Tensor, mom: torch.Tensor, step: int,
@@ -67,6 +72,36 @@ def save(path: str, layout: FlatLayout, params: torch.Tensor, mom: torch.Tensor,
     np.savez(tmp, **arrays)
     os.replace(tmp, path)
     return path
+
+
+def ema_arrays(layout: FlatLayout, ema: torch.Tensor) -> Dict[str, torch.Tensor]:
+    """The `extra` entries of save() that hold the moving average `ema` (a flat
+    buffer in `layout`): `<tf_name>/ExponentialMovingAverage` per parameter."""
+    ev = layout.views(ema.detach())
+    return {s.tf_name + EMA_SUFFIX: ev[s.name] for s in layout.specs}
+
+
+@torch.no_grad()
+def load_ema(path: str, layout: FlatLayout, ema: torch.Tensor) -> Tuple[bool, Optional[str]]:
+    """Loads the moving average of a checkpoint into the flat buffer `ema` in
+    place -> (found, the saved spec or None).  A checkpoint written without
+    --ema has none of the arrays: `ema` is left alone and found is False;
+    one that has only some of them is broken."""
+    with np.load(path, allow_pickle=False) as z:
+        spec = str(z[META_PREFIX + EMA_META]) if META_PREFIX + EMA_META in z.files else None
+        keys = [s.tf_name + EMA_SUFFIX for s in layout.specs]
+        have = [k in z.files for k in keys]
+        if not any(have):
+            return False, spec
+        if not all(have):
+            raise ValueError(f"{path}: missing {keys[have.index(False)]}")
+        ev = layout.views(ema.detach())
+        for s, k in zip(layout.specs, keys):
+            a = z[k]
+            if tuple(a.shape) != tuple(s.shape):
+                raise ValueError(f"{path}: {k} ({s.name}) has shape {a.shape}, expected {s.shape}")
+            ev[s.name].copy_(torch.from_numpy(np.ascontiguousarray(a, np.float32)))
+    return True, spec
 
 
 @torch.no_grad()

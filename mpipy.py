@@ -10,13 +10,14 @@ module global, /root/reference/mpipy.py:14-21).  Here:
 with optional overrides (see --help): --epochs, --batch-size, --model
 {mnist_cnn,lenet5,resnet18}, --sync {grad,param_avg,none}, --sync-every,
 --eval-every, --synthetic, --ckpt/--resume, --metrics-jsonl,
---eval-metrics, --ckpt-best, --reference-quirks.  Log lines keep the reference's exact formats.
+--eval-metrics, --ckpt-best, --ema, --reference-quirks.  Log lines keep the reference's exact formats.
 
     python mpipy.py --resume best.npz --predict test           # evaluate a checkpoint
     python mpipy.py --resume best.npz --predict digits.npy --predict-out p.npz
 
 classify instead of training (--predict SRC, --predict-labels, --predict-out,
---predict-topk, --predict-tta, --predict-probs; runtime/predict.py).
+--predict-topk, --predict-tta, --predict-probs, --predict-weights;
+runtime/predict.py).
 """
 
 from __future__ import annotations
