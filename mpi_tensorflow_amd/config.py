@@ -92,20 +92,41 @@ MAX_TTA_SHIFT = 3
 PREDICT_WEIGHTS = ("raw", "ema")
 
 
-def parse_augment(spec: str, model: str = "mnist_cnn"):
-    """`shift:K` (K >= 1), `flip` and optionally `fill:V`, comma separated, in
-    any order, each at most once -> (K, flip, fill); K = 0 without a shift."""
+MAX_ROTATE, MAX_SCALE = 45.0, 50.0  # degrees, percent: the largest rotate:D and scale:P
+
+
+@dataclasses.dataclass(frozen=True)
+class AugmentSpec:
+    """A parsed --augment spec; rotate / scale / cutout are 0 when absent."""
+    K: int
+    flip: bool
+    fill: float
+    rotate: float = 0.0  # degrees either way
+    scale: float = 0.0   # percent either way
+    cutout: int = 0      # side of the erased square
+
+    @property
+    def affine(self) -> bool:
+        """Needs the affine load (rotate, scale or cutout), not only shift / flip."""
+        return self.rotate > 0 or self.scale > 0 or self.cutout > 0
+
+
+def parse_augment_spec(spec: str, model: str = "mnist_cnn") -> AugmentSpec:
+    """`shift:K` (K >= 1), `flip`, `rotate:D` (0 < D <= 45 degrees), `scale:P`
+    (0 < P <= 50 percent), `cutout:S` (S >= 1) and optionally `fill:V`, comma
+    separated, in any order, each at most once, at least one of the first five."""
     if not isinstance(spec, str) or not spec.strip():
-        raise ValueError("empty augment spec; expected e.g. 'shift:2', 'shift:4,flip', 'flip'")
+        raise ValueError("empty augment spec; expected e.g. 'shift:2', 'shift:4,flip', 'flip', "
+                         "'shift:2,rotate:10,scale:10'")
     seen = {}
     for item in spec.split(","):
         name, sep, val = item.strip().partition(":")
         if name in seen:
             raise ValueError(f"augment spec {spec!r} names {name!r} twice")
         try:
-            if name == "shift" and sep:
+            if name in ("shift", "cutout") and sep:
                 seen[name] = int(val)
-            elif name == "fill" and sep:
+            elif name in ("fill", "rotate", "scale") and sep:
                 seen[name] = float(val)
                 if seen[name] != seen[name] or abs(seen[name]) == float("inf"):
                     raise ValueError
@@ -115,13 +136,33 @@ def parse_augment(spec: str, model: str = "mnist_cnn"):
                 raise ValueError
         except ValueError:
             raise ValueError(f"bad item {item!r} in augment spec {spec!r}; expected shift:K, "
-                             f"flip or fill:V") from None
+                             f"flip, rotate:D, scale:P, cutout:S or fill:V") from None
     K = seen.get("shift", 0)
     if "shift" in seen and K < 1:
         raise ValueError(f"augment shift must be at least 1, got {K}")
-    if "shift" not in seen and "flip" not in seen:
-        raise ValueError(f"augment spec {spec!r} asks for neither a shift nor a flip")
-    return K, "flip" in seen, float(seen.get("fill", AUGMENT_FILL.get(model, 0.0)))
+    if "rotate" in seen and not 0.0 < seen["rotate"] <= MAX_ROTATE:
+        raise ValueError(f"augment rotate must be in (0, {MAX_ROTATE:g}] degrees, got "
+                         f"{seen['rotate']:g}")
+    if "scale" in seen and not 0.0 < seen["scale"] <= MAX_SCALE:
+        raise ValueError(f"augment scale must be in (0, {MAX_SCALE:g}] percent, got "
+                         f"{seen['scale']:g}")
+    if "cutout" in seen and seen["cutout"] < 1:
+        raise ValueError(f"augment cutout must be at least 1, got {seen['cutout']}")
+    if not any(k in seen for k in ("shift", "flip", "rotate", "scale", "cutout")):
+        raise ValueError(f"augment spec {spec!r} asks for none of shift, flip, rotate, scale, "
+                         f"cutout")
+    return AugmentSpec(K, "flip" in seen, float(seen.get("fill", AUGMENT_FILL.get(model, 0.0))),
+                       seen.get("rotate", 0.0), seen.get("scale", 0.0), seen.get("cutout", 0))
+
+
+def parse_augment(spec: str, model: str = "mnist_cnn"):
+    """The shift / flip subset of `parse_augment_spec` (test-time augmentation
+    takes no other item) -> (K, flip, fill); K = 0 without a shift."""
+    s = parse_augment_spec(spec, model)
+    if s.affine:
+        raise ValueError(f"augment spec {spec!r}: rotate, scale and cutout are training-only "
+                         f"(--augment); here only shift:K, flip and fill:V apply")
+    return s.K, s.flip, s.fill
 
 
 def parse_ema(spec: str):
@@ -214,8 +255,9 @@ class TrainConfig:
     # a new row order for every pass over the local shard (runtime/shuffle.py);
     # off = the reference's file order (mpipy.py:80), the same batches every pass
     shuffle: bool = False
-    # per-pass random shift / horizontal flip of the training images, redrawn
-    # for every row and pass on the device (parse_augment, runtime/shuffle.py);
+    # per-pass random shift / horizontal flip / rotation / zoom / cutout of the
+    # training images, redrawn for every row and pass on the device
+    # (parse_augment_spec, runtime/shuffle.py);
     # None = every pass shows the same pixels
     augment: Optional[str] = None
     # exponential moving average of the weights, updated on the device after
@@ -301,7 +343,7 @@ class TrainConfig:
         if not 0.0 < self.dropout_keep <= 1.0:
             raise ValueError("dropout_keep must be in (0, 1]")
         if self.augment is not None:
-            parse_augment(self.augment, self.model)
+            parse_augment_spec(self.augment, self.model)
         if self.ema is not None:
             parse_ema(self.ema)
             if self.model == "resnet18":
@@ -421,9 +463,11 @@ def build_arg_parser(prog: str = "mpipy.py") -> argparse.ArgumentParser:
                    help="permute each rank's shard anew for every pass (on the device, a pure "
                         "function of seed, rank and pass; the reference reads in file order)")
     p.add_argument("--augment", default=d.augment, metavar="SPEC",
-                   help="random shift and / or horizontal flip of every training image, redrawn "
-                        "each pass on the device: shift:K[,flip][,fill:V] or flip (fill: the value "
-                        "shifted in, default -0.5 for mnist_cnn, 0 otherwise)")
+                   help="random shift, horizontal flip, rotation, zoom and erased square of every "
+                        "training image, redrawn each pass on the device: any of shift:K, flip, "
+                        "rotate:D (degrees either way, at most 45), scale:P (percent either way, "
+                        "at most 50), cutout:S (an S x S square), and fill:V (the value shifted, "
+                        "turned or cut in, default -0.5 for mnist_cnn, 0 otherwise)")
     p.add_argument("--ema", default=d.ema, metavar="SPEC",
                    help="keep an exponential moving average of the weights on the device: "
                         "DECAY[,every:K] (0 < DECAY < 1, updated after every K-th step with TF's "

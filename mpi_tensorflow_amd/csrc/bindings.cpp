@@ -797,6 +797,19 @@ PYBIND11_MODULE(_C, m) {
   }, py::arg("src_x"), py::arg("src_y"), py::arg("dst_x"), py::arg("dst_y"), py::arg("n"),
      py::arg("H"), py::arg("W"), py::arg("C"), py::arg("use_perm"), py::arg("perm_key"),
      py::arg("aug_key"), py::arg("K"), py::arg("flip"), py::arg("fill"), py::arg("st"));
+  // ... with rotate / scale / cutout: the affine load (tables: 3 x 129 device int32)
+  g.def("affine_rows", [](uintptr_t src_x, uintptr_t src_y, uintptr_t dst_x, uintptr_t dst_y,
+                          long long n, int H, int W, int C, bool use_perm, uint32_t perm_key,
+                          uint32_t aug_key, int K, bool flip, float fill, uintptr_t tables, int cutout,
+                          uintptr_t st) {
+    augment::affine_rows(P<const float>(src_x), P<const int>(src_y), P<float>(dst_x), P<int>(dst_y),
+                         n, H, W, C, use_perm, perm_key, aug_key, K, flip, fill,
+                         P<const int>(tables), cutout, S(st));
+    check_launch();
+  }, py::arg("src_x"), py::arg("src_y"), py::arg("dst_x"), py::arg("dst_y"), py::arg("n"),
+     py::arg("H"), py::arg("W"), py::arg("C"), py::arg("use_perm"), py::arg("perm_key"),
+     py::arg("aug_key"), py::arg("K"), py::arg("flip"), py::arg("fill"), py::arg("tables"),
+     py::arg("S"), py::arg("st"));
   // inference (kernels/predict.h): one view of the input rows, the prediction head
   g.def("predict_prep", [](uintptr_t src, bool src_u8, uintptr_t dst, long long n, int H, int W,
                            int C, int dy, int dx, bool flip, float fill, uintptr_t lut,

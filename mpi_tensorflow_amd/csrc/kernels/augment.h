@@ -23,4 +23,25 @@ void augment_rows(const float* src_x, const int* src_y, float* dst_x, int* dst_y
                   int H, int W, int C, bool use_perm, uint32_t perm_key, uint32_t aug_key, int K,
                   bool flip, float fill, hipStream_t st);
 
+// The same load with a random rotation, zoom and erased square on top (rotate:D,
+// scale:P, cutout:S): a per-row inverse affine map with bilinear sampling.  The
+// draw chain goes on, h_{k+1} = mix32(h_k + GOLDEN) up to h6:
+//   ia = h3 % 129, ib = h4 % 129    levels into `tables` = cosT | sinT | invT,
+//                                   3 x 129 device int32 in Q16 (rng.affine_tables)
+//   cy0 = h5 % (H - S + 1), cx0 = h6 % (W - S + 1)    the cutout's corner, S > 0
+//   m00 = m11 = r(cosT[ia] invT[ib]), m01 = r(sinT[ia] invT[ib]),
+//   m10 = r(-sinT[ia] invT[ib]),  r(v) = (v + 32768) >> 16 in 64 bits
+// Source coordinate of output pixel (y, x) in Q17, u2 = 2x - (W-1), v2 = 2y - (H-1):
+//   SX = m00 u2 + m01 v2 + ((W-1) << 16); flipped: SX = ((W-1) << 17) - SX; SX += dx << 17
+//   SY = m10 u2 + m11 v2 + ((H-1) << 16);                                   SY += dy << 17
+//   ix = SX >> 17, fx = (SX & 0x1FFFF) 2^-17, likewise iy, fy; taps outside = fill
+//   out = (1 - fy) ((1 - fx) p00 + fx p01) + fy ((1 - fx) p10 + fx p11)
+// with every -, * and + one rounded fp32 operation (no fused multiply-add), and
+// fill inside the cutout square.  Identical to utils/rng.py affine_params /
+// affine_np, bit for bit.  H, W <= 1024 (the coordinates are 32-bit); S = 0: no
+// cutout.  Otherwise the contract of augment_rows.
+void affine_rows(const float* src_x, const int* src_y, float* dst_x, int* dst_y, long long n,
+                 int H, int W, int C, bool use_perm, uint32_t perm_key, uint32_t aug_key, int K,
+                 bool flip, float fill, const int* tables, int S, hipStream_t st);
+
 }  // namespace augment

@@ -14,6 +14,10 @@
 // consecutive 16-byte runs and a wave covers 1 KB of whole lines.  Around the
 // fill border, and in flipped rows (pixel order reversed, channel order kept),
 // the four are single loads: the lines they touch are the same ones.
+//
+// affine_rows (rotate / scale / cutout) keeps that shape; the seven hashes, the
+// table reads and the Q16 matrix are per row and scalar as well, and each
+// destination float is four guarded single loads and seven fp32 operations.
 #include "augment.h"
 
 #include <algorithm>
@@ -136,15 +140,136 @@ __global__ __launch_bounds__(THREADS) void rows_kernel(const float* __restrict__
   }
 }
 
+// ---- rotate / scale / cutout: per-row inverse affine map, bilinear taps ----
+// The draw of a row in the form the lanes use it: SX = ax u2 + bx v2 + cx and
+// SY = ay u2 + by v2 + cy in Q17 pixels (augment.h; a flip negates ax and bx:
+// ((W-1) << 17) - (A + ((W-1) << 16)) = -A + ((W-1) << 16)).  32-bit: with
+// |m| <= 2^17, H, W <= 1024 and |dy|, |dx| < 1024 every sum stays below 2^29.
+struct Row {
+  int ax, bx, cx, ay, by, cy;
+  int cy0, cx0;  // the cutout's corner
+};
+
+constexpr int LEVELS = 129;
+constexpr int MAX_SIDE = 1024;
+
+__device__ __forceinline__ int q16(long long v) { return (int)((v + 32768) >> 16); }
+
+// One destination float: pixel (y, x), channel c of the row whose source row is a.
+__device__ __forceinline__ float sample(const float* __restrict__ a, const Geo& g, const Row& r,
+                                        int S, uint32_t y, uint32_t x, uint32_t c) {
+#pragma clang fp contract(off)  // every *, +, - below is one rounded fp32 operation
+  if (S > 0 && y - (uint32_t)r.cy0 < (uint32_t)S && x - (uint32_t)r.cx0 < (uint32_t)S)
+    return g.fill;
+  const int u2 = 2 * (int)x - (int)(g.W - 1u), v2 = 2 * (int)y - (int)(g.H - 1u);
+  const int sx = r.ax * u2 + r.bx * v2 + r.cx, sy = r.ay * u2 + r.by * v2 + r.cy;
+  const int ix = sx >> 17, iy = sy >> 17;  // floor
+  const float fx = (float)(sx & 0x1FFFF) * 0x1p-17f, fy = (float)(sy & 0x1FFFF) * 0x1p-17f;
+  const bool x0 = (uint32_t)ix < g.W, x1 = (uint32_t)(ix + 1) < g.W;
+  const bool y0 = (uint32_t)iy < g.H, y1 = (uint32_t)(iy + 1) < g.H;
+  const float* q = a + ((long long)iy * (int)g.W + ix) * (int)g.C + (int)c;  // tap (iy, ix)
+  const float p00 = y0 && x0 ? q[0] : g.fill;
+  const float p01 = y0 && x1 ? q[g.C] : g.fill;
+  const float p10 = y1 && x0 ? q[g.wc] : g.fill;
+  const float p11 = y1 && x1 ? q[g.wc + g.C] : g.fill;
+  const float gx = 1.0f - fx, gy = 1.0f - fy;
+  const float t = gx * p00 + fx * p01;
+  const float b = gx * p10 + fx * p11;
+  return gy * t + fy * b;
+}
+
+// As rows_kernel: a workgroup per 16 KB piece of a destination row, the draw in
+// scalar registers, U = 4 floats and one aligned 16-byte store a thread (or U = 1).
+// The taps are read straight from the source row: the 4 floats of a thread and
+// the 4 taps of each share cache lines with their neighbours in the wave.
+template <int U>
+__global__ __launch_bounds__(THREADS) void affine_kernel(const float* __restrict__ src_x,
+                                                         const int* __restrict__ src_y,
+                                                         float* __restrict__ dst_x,
+                                                         int* __restrict__ dst_y, shuffle::Perm p,
+                                                         int use_perm, Geo g,
+                                                         const int* __restrict__ tab, int S,
+                                                         long long row_vecs) {
+  const long long v0 = (long long)blockIdx.y * PIECE + threadIdx.x;
+  const long long row_elems = row_vecs * U;
+  const long long n = p.n;
+  for (long long i = blockIdx.x; i < n; i += gridDim.x) {
+    const uint32_t s = use_perm ? shuffle::perm_of(p, (uint32_t)i) : (uint32_t)i;
+    uint32_t h[7];
+    h[0] = mix32(g.key ^ s);
+#pragma unroll
+    for (int k = 1; k < 7; ++k) h[k] = mix32(h[k - 1] + 0x9E3779B9u);
+    const int dy = (int)(h[0] % g.span) - g.K, dx = (int)(h[1] % g.span) - g.K;
+    const bool fl = g.flip && (h[2] >> 31);
+    const uint32_t ia = h[3] % LEVELS, ib = h[4] % LEVELS;
+    const long long co = tab[ia], si = tab[LEVELS + ia], inv = tab[2 * LEVELS + ib];
+    const int m00 = q16(co * inv), m01 = q16(si * inv), m10 = q16(-si * inv);
+    Row r;
+    r.ax = fl ? -m00 : m00, r.bx = fl ? -m01 : m01;
+    r.cx = (int)((g.W - 1u) << 16) + dx * (1 << 17);
+    r.ay = m10, r.by = m00;
+    r.cy = (int)((g.H - 1u) << 16) + dy * (1 << 17);
+    r.cy0 = S > 0 ? (int)(h[5] % (g.H - (uint32_t)S + 1u)) : 0;
+    r.cx0 = S > 0 ? (int)(h[6] % (g.W - (uint32_t)S + 1u)) : 0;
+    const float* a = src_x + (long long)s * row_elems;
+    float* d = dst_x + i * row_elems;
+    float o[PER_THREAD][U];
+#pragma unroll
+    for (int u = 0; u < PER_THREAD; ++u) {
+      const long long v = v0 + u * THREADS;
+      if (v < row_vecs) {
+        const uint32_t e = (uint32_t)(v * U);
+        uint32_t y = div_by(e, g.wc, g.m_wc);
+        uint32_t x = div_by(e - y * g.wc, g.C, g.m_c);
+        uint32_t c = e - y * g.wc - x * g.C;
+#pragma unroll
+        for (int k = 0; k < U; ++k) {
+          o[u][k] = sample(a, g, r, S, y, x, c);
+          if (++c == g.C) {
+            c = 0;
+            if (++x == g.W) x = 0, ++y;
+          }
+        }
+      }
+    }
+#pragma unroll
+    for (int u = 0; u < PER_THREAD; ++u) {
+      const long long v = v0 + u * THREADS;
+      if (v < row_vecs) {
+        if constexpr (U == 4) {
+          const f32x4 t = {o[u][0], o[u][1], o[u][2], o[u][3]};
+          reinterpret_cast<f32x4*>(d)[v] = t;
+        } else {
+          d[v] = o[u][0];
+        }
+      }
+    }
+    if (src_y && blockIdx.y == 0 && threadIdx.x == 0) dst_y[i] = src_y[s];
+  }
+}
+
+// the grid of both kernels: (rows in flight, 16 KB pieces of a row)
+dim3 rows_grid(const char* who, long long n, long long row_vecs) {
+  const long long pieces = (row_vecs + PIECE - 1) / PIECE;
+  if (pieces > 65535) throw std::runtime_error(std::string(who) + ": row too long");
+  const long long gx = std::max(1ll, std::min(n, MAX_BLOCKS / pieces));
+  return dim3((unsigned)gx, (unsigned)pieces);
+}
+
 template <int U>
 void launch_rows(const float* src_x, const int* src_y, float* dst_x, int* dst_y,
                  const shuffle::Perm& p, bool use_perm, const Geo& g, long long row_vecs,
                  hipStream_t st) {
-  const long long pieces = (row_vecs + PIECE - 1) / PIECE;
-  if (pieces > 65535) throw std::runtime_error("augment_rows: row too long");
-  const long long gx = std::max(1ll, std::min((long long)p.n, MAX_BLOCKS / pieces));
-  rows_kernel<U><<<dim3((unsigned)gx, (unsigned)pieces), THREADS, 0, st>>>(
+  rows_kernel<U><<<rows_grid("augment_rows", p.n, row_vecs), THREADS, 0, st>>>(
       src_x, src_y, dst_x, dst_y, p, use_perm ? 1 : 0, g, row_vecs);
+}
+
+template <int U>
+void launch_affine(const float* src_x, const int* src_y, float* dst_x, int* dst_y,
+                   const shuffle::Perm& p, bool use_perm, const Geo& g, const int* tab, int S,
+                   long long row_vecs, hipStream_t st) {
+  affine_kernel<U><<<rows_grid("affine_rows", p.n, row_vecs), THREADS, 0, st>>>(
+      src_x, src_y, dst_x, dst_y, p, use_perm ? 1 : 0, g, tab, S, row_vecs);
 }
 
 bool overlap(const void* a, const void* b, unsigned long long bytes) {
@@ -152,34 +277,69 @@ bool overlap(const void* a, const void* b, unsigned long long bytes) {
   return x < y + bytes && y < x + bytes;
 }
 
-}  // namespace
-
-void augment_rows(const float* src_x, const int* src_y, float* dst_x, int* dst_y, long long n,
-                  int H, int W, int C, bool use_perm, uint32_t perm_key, uint32_t aug_key, int K,
-                  bool flip, float fill, hipStream_t st) {
-  if (n < 0 || n > 0x7FFFFFFFll) throw std::runtime_error("augment_rows: n out of range");
-  if (H <= 0 || W <= 0 || C <= 0) throw std::runtime_error("augment_rows: H, W, C must be positive");
+// The checks both entries share, thrown before anything is launched; false: nothing to do.
+bool check_rows(const std::string& who, const float* src_x, const int* src_y, float* dst_x,
+                int* dst_y, long long n, int H, int W, int C, int K) {
+  if (n < 0 || n > 0x7FFFFFFFll) throw std::runtime_error(who + ": n out of range");
+  if (H <= 0 || W <= 0 || C <= 0) throw std::runtime_error(who + ": H, W, C must be positive");
   const long long row_elems = (long long)H * W * C;
-  if (row_elems > 0x7FFFFFFFll) throw std::runtime_error("augment_rows: image too large");
+  if (row_elems > 0x7FFFFFFFll) throw std::runtime_error(who + ": image too large");
   if (K < 0 || K >= std::min(H, W))
-    throw std::runtime_error("augment_rows: shift K must be in [0, min(H, W))");
-  if (!src_x || !dst_x || (src_y && !dst_y)) throw std::runtime_error("augment_rows: null buffer");
-  if (n == 0) return;
+    throw std::runtime_error(who + ": shift K must be in [0, min(H, W))");
+  if (!src_x || !dst_x || (src_y && !dst_y)) throw std::runtime_error(who + ": null buffer");
+  if (n == 0) return false;
   if (overlap(src_x, dst_x, (unsigned long long)n * row_elems * sizeof(float)) ||
       (src_y && overlap(src_y, dst_y, (unsigned long long)n * sizeof(int))))
-    throw std::runtime_error("augment_rows: src and dst overlap");
-  const shuffle::Perm p = shuffle::make_perm(perm_key, n);
+    throw std::runtime_error(who + ": src and dst overlap");
+  return true;
+}
+
+Geo make_geo(int H, int W, int C, uint32_t aug_key, int K, bool flip, float fill) {
   Geo g;
   g.H = H, g.W = W, g.C = C, g.wc = (uint32_t)W * C;
   g.m_wc = magic(g.wc), g.m_c = magic(g.C);
   g.key = aug_key, g.span = 2u * K + 1u;
   g.K = K, g.flip = flip ? 1 : 0, g.fill = fill;
-  const bool vec = row_elems % 4 == 0 && (reinterpret_cast<uintptr_t>(src_x) & 15) == 0 &&
-                   (reinterpret_cast<uintptr_t>(dst_x) & 15) == 0;
-  if (vec)
+  return g;
+}
+
+// rows of whole 16-byte vectors between 16-byte aligned bases
+bool vector_rows(const float* src_x, const float* dst_x, long long row_elems) {
+  return row_elems % 4 == 0 && (reinterpret_cast<uintptr_t>(src_x) & 15) == 0 &&
+         (reinterpret_cast<uintptr_t>(dst_x) & 15) == 0;
+}
+
+}  // namespace
+
+void augment_rows(const float* src_x, const int* src_y, float* dst_x, int* dst_y, long long n,
+                  int H, int W, int C, bool use_perm, uint32_t perm_key, uint32_t aug_key, int K,
+                  bool flip, float fill, hipStream_t st) {
+  if (!check_rows("augment_rows", src_x, src_y, dst_x, dst_y, n, H, W, C, K)) return;
+  const long long row_elems = (long long)H * W * C;
+  const shuffle::Perm p = shuffle::make_perm(perm_key, n);
+  const Geo g = make_geo(H, W, C, aug_key, K, flip, fill);
+  if (vector_rows(src_x, dst_x, row_elems))
     launch_rows<4>(src_x, src_y, dst_x, dst_y, p, use_perm, g, row_elems / 4, st);
   else
     launch_rows<1>(src_x, src_y, dst_x, dst_y, p, use_perm, g, row_elems, st);
+}
+
+void affine_rows(const float* src_x, const int* src_y, float* dst_x, int* dst_y, long long n,
+                 int H, int W, int C, bool use_perm, uint32_t perm_key, uint32_t aug_key, int K,
+                 bool flip, float fill, const int* tables, int S, hipStream_t st) {
+  if (H > MAX_SIDE || W > MAX_SIDE)
+    throw std::runtime_error("affine_rows: H, W above 1024 (32-bit source coordinates)");
+  if (!tables) throw std::runtime_error("affine_rows: null table");
+  if (H > 0 && W > 0 && (S < 0 || S >= std::min(H, W)))
+    throw std::runtime_error("affine_rows: cutout S must be in [0, min(H, W))");
+  if (!check_rows("affine_rows", src_x, src_y, dst_x, dst_y, n, H, W, C, K)) return;
+  const long long row_elems = (long long)H * W * C;
+  const shuffle::Perm p = shuffle::make_perm(perm_key, n);
+  const Geo g = make_geo(H, W, C, aug_key, K, flip, fill);
+  if (vector_rows(src_x, dst_x, row_elems))
+    launch_affine<4>(src_x, src_y, dst_x, dst_y, p, use_perm, g, tables, S, row_elems / 4, st);
+  else
+    launch_affine<1>(src_x, src_y, dst_x, dst_y, p, use_perm, g, tables, S, row_elems, st);
 }
 
 }  // namespace augment

@@ -20,6 +20,12 @@ same with and without shuffle, pass 0 included.  On the native path the load
 stays one launch (`augment_rows`, csrc/kernels/augment.hip: the gather and the
 transform in one pass over the shard); with augment alone the order is the
 file order.
+
+A spec with rotate, scale or cutout takes the affine load instead: the same
+draw chain continued (`rng.affine_params`), a per-row inverse affine map with
+bilinear sampling (`rng.affine_np` is the definition), still one launch
+(`affine_rows`), reading one 3 x 129 int32 table uploaded at construction.
+Specs without those items keep the shift / flip load unchanged.
 """
 
 from __future__ import annotations
@@ -49,22 +55,36 @@ class PassShuffler:
     (`work_x` / `work_y`: the engine reads those instead).
 
     `augment`: None or (K, flip, fill, (H, W, C)), the per-pass shift / flip of
-    the NHWC images; `shuffle=False` keeps the file order (augment only)."""
+    the NHWC images, or (config.AugmentSpec, (H, W, C)) for a spec with rotate,
+    scale or cutout (held as `affine`); `shuffle=False` keeps the file order
+    (augment only)."""
 
     def __init__(self, seed: int, rank: int, n_local: int, batch: int, work_x: torch.Tensor,
                  work_y: torch.Tensor, native=None, augment=None, shuffle: bool = True):
         self.seed, self.rank, self.n, self.B = int(seed), int(rank), int(n_local), int(batch)
         self.shuffle = bool(shuffle)
         self.augment = None
+        self.affine = None  # (spec, (H, W, C)) with rotate / scale / cutout in the spec
+        self.tables = None  # ... and rng.affine_tables of it, uploaded once on the native path
         if augment is not None:
-            K, flip, fill, (H, W, C) = augment
-            K, H, W, C = int(K), int(H), int(W), int(C)
+            spec = augment[0] if len(augment) == 2 else None
+            K, flip, fill = (spec.K, spec.flip, spec.fill) if spec is not None else augment[:3]
+            H, W, C = (int(v) for v in augment[-1])
+            K = int(K)
             if K < 0 or K >= min(H, W):
                 raise ValueError(f"augment shift {K} must be below min(H, W) = {min(H, W)}")
             if tuple(work_x.shape[1:]) != (H, W, C):
                 raise ValueError(f"augment: rows of shape {tuple(work_x.shape[1:])}, images "
                                  f"{(H, W, C)}")
-            if K > 0 or flip:
+            if spec is not None and spec.affine:
+                if spec.cutout >= min(H, W):
+                    raise ValueError(f"augment cutout {spec.cutout} must be below min(H, W) = "
+                                     f"{min(H, W)}")
+                self.affine = (spec, (H, W, C))
+                self.tables = rng.affine_tables(spec.rotate, spec.scale)
+                if native is not None:
+                    self.tables = torch.from_numpy(self.tables).to(work_x.device)
+            elif K > 0 or flip:
                 self.augment = (K, bool(flip), float(fill), (H, W, C))
         if native is not None:  # the executors hold the pointers of the working copy
             self.work_x, self.work_y = work_x, work_y
@@ -96,7 +116,14 @@ class PassShuffler:
             return
         if self._C is not None:
             from ..ops import ptr, stream_handle
-            if self.augment is None:
+            if self.affine is not None:
+                spec, (H, W, C) = self.affine
+                self._C.ops.affine_rows(ptr(self.src_x), ptr(self.src_y), ptr(self.work_x),
+                                        ptr(self.work_y), self.n, H, W, C, self.shuffle,
+                                        self.key(p) if self.shuffle else 0, self.augment_key(p),
+                                        spec.K, spec.flip, spec.fill, ptr(self.tables),
+                                        spec.cutout, stream_handle())
+            elif self.augment is None:
                 self._C.ops.shuffle_rows(ptr(self.src_x), ptr(self.src_y), ptr(self.work_x),
                                          ptr(self.work_y), self.n, self.row_elems, self.key(p),
                                          stream_handle())
@@ -112,7 +139,11 @@ class PassShuffler:
             if self.shuffle:
                 idx = torch.from_numpy(rows).to(self.work_x.device)
                 x, y = x[idx], y[idx]
-            if self.augment is not None:
+            if self.affine is not None:
+                spec, (H, W, _) = self.affine
+                q = rng.affine_params(self.augment_key(p), rows, spec, H, W, self.tables)
+                x = rng.affine_torch(x, q.m, q.dy, q.dx, q.flipped, spec.fill, q.cutout)
+            elif self.augment is not None:
                 K, flip, fill, _ = self.augment
                 x = rng.augment_torch(x, *rng.augment_params(self.augment_key(p), rows, K, flip),
                                       fill)
@@ -147,9 +178,10 @@ def make_shuffler(cfg, rank: int, n_local: int, work_x: torch.Tensor, work_y: to
         return None
     augment = None
     if spec is not None:
-        from ..config import parse_augment
+        from ..config import parse_augment_spec
         if image_shape is None:
             raise ValueError("augment needs the image shape of the shard's rows")
-        augment = parse_augment(spec, cfg.model) + (tuple(int(v) for v in image_shape),)
+        s, shape = parse_augment_spec(spec, cfg.model), tuple(int(v) for v in image_shape)
+        augment = (s, shape) if s.affine else (s.K, s.flip, s.fill, shape)
     return PassShuffler(cfg.seed, rank, n_local, cfg.batch_size, work_x, work_y, native,
                         augment=augment, shuffle=shuffle)

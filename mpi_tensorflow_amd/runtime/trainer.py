@@ -365,10 +365,14 @@ class Trainer:
             off = batch_offset(step, n, B)
             rows = np.arange(off, off + B)
         x = sh.train_x[rows]
-        if cfg.augment is not None:  # ... with this pass's shift / flip of each of them
-            K, flip, fill = C.parse_augment(cfg.augment, cfg.model)
+        if cfg.augment is not None:  # ... with this pass's draws for each of them
+            spec = C.parse_augment_spec(cfg.augment, cfg.model)
             key = rng.augment_key(cfg.seed, rank, pass_of(step, n, B))
-            x = rng.augment_np(x, *rng.augment_params(key, rows, K, flip), fill)
+            if spec.affine:
+                q = rng.affine_params(key, rows, spec, *x.shape[1:3])
+                x = rng.affine_np(x, q.m, q.dy, q.dx, q.flipped, spec.fill, q.cutout)
+            else:
+                x = rng.augment_np(x, *rng.augment_params(key, rows, spec.K, spec.flip), spec.fill)
         return self.eval_prediction(x, dropout=True)
 
     def check_replicas(self, step: int, averaged: bool = False) -> None:

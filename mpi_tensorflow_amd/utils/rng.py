@@ -19,6 +19,8 @@ side lives in `csrc/kernels/common.h` (`dropout_key`, `dropout_keep`).
 
 from __future__ import annotations
 
+from typing import NamedTuple, Optional, Tuple
+
 import numpy as np
 
 M32 = 0xFFFFFFFF
@@ -142,6 +144,179 @@ def augment_torch(x_nhwc, dy, dx, flip, fill: float):
     got = x[torch.arange(n, device=dev)[:, None, None], ys.clamp(0, H - 1)[:, :, None],
             xs.clamp(0, W - 1)[:, None, :]]
     return torch.where(inside, got, torch.full((), fill, dtype=x.dtype, device=dev))
+
+
+# ---- rotate / scale / cutout (--augment rotate:D, scale:P, cutout:S) --------
+# Integer coordinates (Q16 matrix, Q17 pixels) and single fp32 operations per
+# sample, so numpy, torch and csrc/kernels/augment.hip agree bit for bit; the
+# definition is spelled out in docs/ACCURACY.md.
+AFFINE_LEVELS = 129  # angle / scale levels, level 64 is the identity
+Q16 = 1 << 16
+
+
+def affine_tables(D: float, P: float) -> np.ndarray:
+    """int32 [3, 129]: cosT, sinT, invT of the levels i = 0..128, a = (i - 64) / 64:
+    rint(cos(radians(D a)) 2^16), rint(sin(radians(D a)) 2^16), rint(2^16 / (1 + P a / 100)),
+    computed in float64.  The oracle and the kernel read this one table."""
+    a = (np.arange(AFFINE_LEVELS, dtype=np.float64) - 64.0) / 64.0
+    ang = np.radians(float(D) * a)
+    return np.stack([np.rint(np.cos(ang) * Q16), np.rint(np.sin(ang) * Q16),
+                     np.rint(Q16 / (1.0 + float(P) * a / 100.0))]).astype(np.int32)
+
+
+class AffineParams(NamedTuple):
+    """The draws of `affine_params`: per row dy, dx (int64), flipped (bool),
+    m (int64 [n, 4]: m00, m01, m10, m11 in Q16), the levels ia, ib behind m, and
+    cutout = (S, cy0, cx0) or None."""
+    dy: np.ndarray
+    dx: np.ndarray
+    flipped: np.ndarray
+    m: np.ndarray
+    ia: np.ndarray
+    ib: np.ndarray
+    cutout: Optional[Tuple[int, np.ndarray, np.ndarray]]
+
+
+def affine_params(key: int, rows, spec, H: int, W: int, tables=None) -> AffineParams:
+    """The draws of the pristine shard rows `rows` under `key` for `spec`
+    (K, flip, rotate, scale, cutout: config.AugmentSpec): the chain of
+    `augment_params` continued, h_{k+1} = mix(h_k + GOLDEN) up to h6.
+
+        dy, dx, flipped from h0, h1, h2 as in `augment_params`
+        ia = h3 % 129, ib = h4 % 129        (levels of `affine_tables`)
+        cy0 = h5 % (H - S + 1), cx0 = h6 % (W - S + 1)
+        m00 = m11 = r(cosT[ia] invT[ib]), m01 = r(sinT[ia] invT[ib]),
+        m10 = r(-sinT[ia] invT[ib]),  r(v) = (v + 32768) >> 16 in 64 bits
+    """
+    s = np.asarray(rows).astype(np.uint64)
+    dy, dx, fl = augment_params(key, s, spec.K, spec.flip)
+    h = _mix_np(s ^ np.uint64(key))
+    hs = [h]
+    for _ in range(6):
+        h = _mix_np(h + np.uint64(GOLDEN))
+        hs.append(h)
+    T = affine_tables(spec.rotate, spec.scale) if tables is None else np.asarray(tables)
+    T = T.astype(np.int64).reshape(3, AFFINE_LEVELS)
+    ia = (hs[3] % np.uint64(AFFINE_LEVELS)).astype(np.int64)
+    ib = (hs[4] % np.uint64(AFFINE_LEVELS)).astype(np.int64)
+    co, si, inv = T[0][ia], T[1][ia], T[2][ib]
+    m00 = (co * inv + 32768) >> 16
+    m = np.stack([m00, (si * inv + 32768) >> 16, (-si * inv + 32768) >> 16, m00], axis=-1)
+    cutout = None
+    S = int(spec.cutout)
+    if S > 0:
+        cutout = (S, (hs[5] % np.uint64(H - S + 1)).astype(np.int64),
+                  (hs[6] % np.uint64(W - S + 1)).astype(np.int64))
+    return AffineParams(dy, dx, fl, m, ia, ib, cutout)
+
+
+def affine_coords(xp, m, dy, dx, fl, H: int, W: int):
+    """Source coordinate of every output pixel in Q17 pixels, (SX, SY), int64
+    [n, H, W] (`xp`: numpy or torch; m [n, 4], dy, dx int64 and fl bool of it).
+
+        u2 = 2x - (W-1), v2 = 2y - (H-1)
+        SX = m00 u2 + m01 v2 + ((W-1) << 16);  flipped: SX = ((W-1) << 17) - SX;  SX += dx << 17
+        SY = m10 u2 + m11 v2 + ((H-1) << 16);  SY += dy << 17
+    """
+    kw = {} if xp is np else {"device": m.device}
+    u2 = (2 * xp.arange(W, **kw) - (W - 1))[None, None, :]
+    v2 = (2 * xp.arange(H, **kw) - (H - 1))[None, :, None]
+    c = [m[:, k][:, None, None] for k in range(4)]
+    SX = c[0] * u2 + c[1] * v2 + ((W - 1) << 16)
+    SY = c[2] * u2 + c[3] * v2 + ((H - 1) << 16)
+    SX = xp.where(fl[:, None, None], ((W - 1) << 17) - SX, SX)
+    return SX + (dx[:, None, None] << 17), SY + (dy[:, None, None] << 17)
+
+
+def _affine_chunk(n: int, H: int, W: int) -> int:
+    return max(1, min(n, (1 << 21) // (H * W)))  # rows a slice: the int64 planes stay small
+
+
+def affine_np(x_nhwc: np.ndarray, m, dy, dx, flipped, fill: float, cutout=None) -> np.ndarray:
+    """Per-row inverse affine map with bilinear sampling, then the cutout.
+    With (ix, fx) = (SX >> 17, (SX & 0x1FFFF) 2^-17) of `affine_coords`, the
+    same for (iy, fy), and taps outside the image = `fill`:
+
+        t = (1 - fx) src[iy][ix] + fx src[iy][ix+1]
+        b = (1 - fx) src[iy+1][ix] + fx src[iy+1][ix+1]
+        out = (1 - fy) t + fy b        every -, *, + one fp32 operation
+
+    `cutout` = (S, cy0, cx0): out = fill for cy0 <= y < cy0 + S, cx0 <= x < cx0 + S."""
+    x = np.asarray(x_nhwc)
+    n, H, W, _ = x.shape
+    m, dy, dx = np.asarray(m, np.int64).reshape(n, 4), np.asarray(dy, np.int64), np.asarray(dx, np.int64)
+    fl = np.asarray(flipped, bool)
+    f32, fv = np.float32, x.dtype.type(fill)
+    out = np.empty_like(x)
+    step = _affine_chunk(n, H, W)
+    for a in range(0, n, step):
+        z = slice(a, min(n, a + step))
+        SX, SY = affine_coords(np, m[z], dy[z], dx[z], fl[z], H, W)
+        ix, iy = SX >> 17, SY >> 17
+        fx = ((SX & 0x1FFFF).astype(f32) * f32(2.0 ** -17))[..., None]
+        fy = ((SY & 0x1FFFF).astype(f32) * f32(2.0 ** -17))[..., None]
+        rows = np.arange(z.start, z.stop)[:, None, None]
+
+        def tap(ty, tx):
+            inside = ((ty >= 0) & (ty < H) & (tx >= 0) & (tx < W))[..., None]
+            return np.where(inside, x[rows, ty.clip(0, H - 1), tx.clip(0, W - 1)], fv)
+
+        gx, gy = f32(1) - fx, f32(1) - fy
+        t = gx * tap(iy, ix) + fx * tap(iy, ix + 1)
+        b = gx * tap(iy + 1, ix) + fx * tap(iy + 1, ix + 1)
+        o = gy * t + fy * b
+        if cutout is not None:
+            S, cy0, cx0 = cutout
+            cy = np.asarray(cy0, np.int64)[z, None, None]
+            cx = np.asarray(cx0, np.int64)[z, None, None]
+            ys, xs = np.arange(H)[None, :, None], np.arange(W)[None, None, :]
+            hole = (ys >= cy) & (ys < cy + S) & (xs >= cx) & (xs < cx + S)
+            o = np.where(hole[..., None], fv, o)
+        out[z] = o
+    return out
+
+
+def affine_torch(x_nhwc, m, dy, dx, flipped, fill: float, cutout=None):
+    """`affine_np` on a torch tensor, on its device (the parameters: numpy)."""
+    import torch
+
+    x = x_nhwc
+    n, H, W, _ = x.shape
+    dev = x.device
+
+    def dev64(v, shape=(-1,)):
+        return torch.from_numpy(np.ascontiguousarray(np.asarray(v, np.int64)).reshape(shape)).to(dev)
+
+    m, dy, dx = dev64(m, (n, 4)), dev64(dy), dev64(dx)
+    fl = torch.from_numpy(np.ascontiguousarray(np.asarray(flipped, bool))).to(dev)
+    fv = torch.full((), fill, dtype=x.dtype, device=dev)
+    out = torch.empty_like(x)
+    step = _affine_chunk(n, H, W)
+    for a in range(0, n, step):
+        z = slice(a, min(n, a + step))
+        SX, SY = affine_coords(torch, m[z], dy[z], dx[z], fl[z], H, W)
+        ix, iy = SX >> 17, SY >> 17
+        fx = ((SX & 0x1FFFF).to(torch.float32) * 2.0 ** -17)[..., None]
+        fy = ((SY & 0x1FFFF).to(torch.float32) * 2.0 ** -17)[..., None]
+        rows = torch.arange(z.start, z.stop, device=dev)[:, None, None]
+
+        def tap(ty, tx):
+            inside = ((ty >= 0) & (ty < H) & (tx >= 0) & (tx < W))[..., None]
+            return torch.where(inside, x[rows, ty.clamp(0, H - 1), tx.clamp(0, W - 1)], fv)
+
+        gx, gy = 1.0 - fx, 1.0 - fy
+        t = gx * tap(iy, ix) + fx * tap(iy, ix + 1)
+        b = gx * tap(iy + 1, ix) + fx * tap(iy + 1, ix + 1)
+        o = gy * t + fy * b
+        if cutout is not None:
+            S, cy0, cx0 = cutout
+            cy, cx = dev64(cy0)[z, None, None], dev64(cx0)[z, None, None]
+            ys = torch.arange(H, device=dev)[None, :, None]
+            xs = torch.arange(W, device=dev)[None, None, :]
+            hole = (ys >= cy) & (ys < cy + S) & (xs >= cx) & (xs < cx + S)
+            o = torch.where(hole[..., None], fv, o)
+        out[z] = o
+    return out
 
 
 def keep_mask_np(key: int, n: int, keep_prob: float) -> np.ndarray:

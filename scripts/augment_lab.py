@@ -1,5 +1,6 @@
 """What the per-pass augmentation launch costs: `augment_rows` (shuffle + shift /
-flip in one pass) against `shuffle_rows` on the three device-resident shards.
+flip in one pass) and `affine_rows` (the same with rotate:10,scale:10 on top)
+against `shuffle_rows` on the three device-resident shards.
 
 Method of PERF_NOTES round 10: HIP events around 100 launches, 10 blocks of
 each kernel alternating after 20 warm-up launches of both; median and range of
@@ -17,6 +18,7 @@ import torch
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 
 from mpi_tensorflow_amd.ops import native, ptr, stream_handle  # noqa: E402
+from mpi_tensorflow_amd.utils import rng  # noqa: E402
 
 SHARDS = (("MNIST", 55000, (28, 28, 1), 2, False, -0.5),
           ("LeNet-5", 8192, (32, 32, 3), 4, True, 0.0),
@@ -46,12 +48,17 @@ def main():
         dst_x, dst_y = torch.empty_like(src_x), torch.empty_like(src_y)
         st = stream_handle()
         args = (ptr(src_x), ptr(src_y), ptr(dst_x), ptr(dst_y), n)
+        tables = torch.from_numpy(rng.affine_tables(10.0, 10.0)).to(dev)
         kernels = {
             "shuffle_rows": lambda: ops.shuffle_rows(*args, row, PERM_KEY, st),
             "augment_rows": lambda: ops.augment_rows(*args, *shape, True, PERM_KEY, AUG_KEY, K,
                                                      flip, fill, st),
             "augment_rows, file order": lambda: ops.augment_rows(*args, *shape, False, 0, AUG_KEY,
                                                                  K, flip, fill, st),
+            "affine_rows": lambda: ops.affine_rows(*args, *shape, True, PERM_KEY, AUG_KEY, K,
+                                                   flip, fill, ptr(tables), 0, st),
+            "affine_rows, file order": lambda: ops.affine_rows(*args, *shape, False, 0, AUG_KEY, K,
+                                                               flip, fill, ptr(tables), 0, st),
         }
         for fn in kernels.values():
             for _ in range(WARM):
