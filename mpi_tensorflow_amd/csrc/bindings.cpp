@@ -281,6 +281,11 @@ PYBIND11_MODULE(_C, m) {
   });
   k.def("set_fc_chain", &mnist::set_fc_chain);
   k.def("fc_chain", &mnist::fc_chain);
+  k.def("set_wgrad_form", &mnist::set_wgrad_form);
+  k.def("wgrad_form", &mnist::wgrad_form);
+  k.attr("WGRAD_TAIL") = mnist::WGRAD_TAIL;
+  k.attr("WGRAD_BASES") = mnist::WGRAD_BASES;
+  k.attr("WGRAD_DEFAULT") = mnist::WGRAD_DEFAULT;
   k.attr("FC_CHAIN_HEAD") = mnist::FC_CHAIN_HEAD;
   k.attr("FC_CHAIN_FWD") = mnist::FC_CHAIN_FWD;
   k.attr("FC_CHAIN_FWD_LOADS") = mnist::FC_CHAIN_FWD_LOADS;

@@ -144,6 +144,16 @@ constexpr int FC_CHAIN_FWD_LOADS = 8;  // fc1_fwd_t_kernel<, UPFRONT>
 constexpr int FC_CHAIN_DEFAULT = FC_CHAIN_HEAD | FC_CHAIN_FWD | FC_CHAIN_FWD_LOADS;
 void set_fc_chain(int mask);
 int fc_chain();
+// The same for the Winograd conv2 filter gradient (bwd_filter_wino_block, as a
+// launch of its own and as the role of launch_conv2_bwd_wino): a mask of the
+// shorter forms, each a template instantiation picked at launch; every form
+// writes the same bits.  mask < 0: back to the default.
+constexpr int WGRAD_TAIL = 1;  // output transform + stores on all 12 waves
+constexpr int WGRAD_BASES = 2;  // main loop: a base per LDS row (columns as immediate
+                               // offsets), zero rows in place of the pad selects
+constexpr int WGRAD_DEFAULT = WGRAD_TAIL | WGRAD_BASES;
+void set_wgrad_form(int mask);
+int wgrad_form();
 // labs: per-block [start, end] 100 MHz clock stamps of the three FC launches
 // into p: 3 regions (fc1 forward, head, fc1 backward) of 2 x 1024 u64, block
 // slots in logical (role) order; zero it before a step; null turns them off
@@ -184,7 +194,7 @@ size_t part2_floats_wino(int batch);
 void launch_conv2_bwd_filter_wino(const float* a1p, const float* dy2, int batch, float* part2,
                                   hipStream_t s, const C1FilterArgs* c1 = nullptr,
                                   const float* dp2 = nullptr, const uint8_t* idx2 = nullptr);
-// phase timing of the above (s_memtime per wave, [blocks][waves][5]); labs only
+// phase timing of the above (s_memtime per wave, [blocks][waves][6]); labs only
 void launch_conv2_bwd_filter_wino_prof(const float* a1p, const float* dy2, int batch,
                                        float* part2, unsigned long long* prof, hipStream_t s,
                                        const float* dp2 = nullptr, const uint8_t* idx2 = nullptr);

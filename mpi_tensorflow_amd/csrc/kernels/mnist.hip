@@ -1956,12 +1956,85 @@ constexpr int WF_DS = WF_IMG * 14 * 16 * WF_DLD;  // [img][row][co][col]
 constexpr int WF_SMEM = WF_XS + WF_DS;
 static_assert(6 * 2 * 5 * 4 * 64 <= WF_SMEM, "S_ah reduction reuses the slices");
 
+// Zero dY rows for the pad rows and the missing image of a partial group
+// (WGRAD_BASES): two rows 16 WF_DLD apart, every channel reads the same words.
+constexpr int WF_ZR = 16 * WF_DLD + 16;
+
+// One row set (4 tile rows, one per lane quad) of the wave's point row, the
+// WGRAD_BASES form: the float expressions are wino_wgrad_row's below, term for
+// term; what changes is integer work only.  Each LDS row the window touches
+// gets a base the compiler cannot fold back into one register + constant, so
+// every read takes its column as an immediate offset (the older form spends a
+// v_add_u32 per ds_read2_b64 on offsets past the instruction's 2040 B), and
+// the pad lanes read zero rows (r0 = r1 = +0 either way: al0 0 + al1 0).
 template <int A>
+__device__ __forceinline__ void wino_wgrad_set(const float* __restrict__ xs,
+                                               const float* __restrict__ dys,
+                                               const float* __restrict__ zr, int nimg, int m,
+                                               int kq, int ch, f32x4 (&acc)[6]) {
+  constexpr float al0 = wino::kAT[0][A], al1 = wino::kAT[1][A];
+  static_assert(WF_IMG == 2, "img = Rc / 7 as a compare");
+  const int R = 4 * m + kq, Rc = min(R, WF_ROWS - 1);
+  const int img = Rc >= 7 ? 1 : 0, ty = Rc - 7 * img;
+  const bool ok = R < WF_ROWS && img < nimg;
+  int xo[6];
+#pragma unroll
+  for (int i = 0; i < 6; ++i) {
+    xo[i] = ((img * 18 + 2 * ty + i) * 16 + ch) * WF_XLD;
+    asm("" : "+v"(xo[i]));
+  }
+  int d0o = ok ? (int)(dys - xs) + ((img * 14 + 2 * ty) * 16 + ch) * WF_DLD : (int)(zr - xs);
+  int d1o = d0o + 16 * WF_DLD;
+  asm("" : "+v"(d0o));
+  asm("" : "+v"(d1o));
+  auto colpair = [&](int pc, float& c0, float& c1) {
+    c0 = 0.f;
+    c1 = 0.f;
+#pragma unroll
+    for (int i = 0; i < 6; ++i) {
+      if (wino::kBT[A][i] == 0.f) continue;
+      const float2 x = *reinterpret_cast<const float2*>(xs + xo[i] + 2 * pc);
+      c0 += wino::kBT[A][i] * x.x;
+      c1 += wino::kBT[A][i] * x.y;
+    }
+  };
+  float t[6];
+  colpair(0, t[0], t[1]);
+  colpair(1, t[2], t[3]);
+#pragma unroll
+  for (int tx = 0; tx < 7; ++tx) {
+    if (tx > 0) {
+      t[0] = t[2];
+      t[1] = t[3];
+      t[2] = t[4];
+      t[3] = t[5];
+    }
+    colpair(tx + 2, t[4], t[5]);
+    float v[6];
+    wino::bt6<1, 1>(t, v);
+    const int ds = 2 * tx;
+    const float2 d0 = *reinterpret_cast<const float2*>(xs + d0o + ds);
+    const float2 d1 = *reinterpret_cast<const float2*>(xs + d1o + ds);
+    const float r0 = al0 * d0.x + al1 * d1.x, r1 = al0 * d0.y + al1 * d1.y;
+    const float u[6] = {r0, r0 + r1, r0 - r1, r0 + 2.f * r1, r0 - 0.5f * r1, r1};
+#pragma unroll
+    for (int b = 0; b < 6; ++b) acc[b] = mfma16x16x4(v[b], u[b], acc[b]);
+  }
+}
+
+template <int A, bool BASES = false>
 __device__ __forceinline__ void wino_wgrad_row(const float* __restrict__ xs,
                                                const float* __restrict__ dys, int nimg,
                                                int lane, int half, f32x4 (&acc)[6]) {
   const int kq = lane >> 4, ch = lane & 15;
   constexpr float al0 = wino::kAT[0][A], al1 = wino::kAT[1][A];
+  if constexpr (BASES) {
+    const float* zr = xs + WF_SMEM;
+#pragma unroll 1
+    for (int m = half * (WF_SETS / 2); m < (half + 1) * (WF_SETS / 2); ++m)
+      wino_wgrad_set<A>(xs, dys, zr, nimg, m, kq, ch, acc);
+    return;
+  }
 #pragma unroll 1
   for (int m = half * (WF_SETS / 2); m < (half + 1) * (WF_SETS / 2); ++m) {
     const int R = 4 * m + kq, Rc = min(R, WF_ROWS - 1);
@@ -2008,24 +2081,55 @@ __device__ __forceinline__ void wino_wgrad_row(const float* __restrict__ xs,
   }
 }
 
-// PROF: per-wave s_memtime stamps at the phase boundaries -> prof[block][wave][5]
-// (scripts/wino_lab.py --phases; never used by the executor)
+// Output transform of columns kw in [KW0, KW1) of element (j, lane' = l):
+// dW[kh][kw] = sum_a G[a][kh] (S_a0 + S_a1)[kw], the expressions and the term
+// order of the tid < 256 form in bwd_filter_wino_block (no FMA contraction).
+template <int KW0, int KW1>
+__device__ __forceinline__ void wino_wgrad_out(const float* __restrict__ red, int j, int l,
+                                               float* __restrict__ out) {
+#pragma clang fp contract(off)
+  float S[6][KW1 - KW0];
+#pragma unroll
+  for (int a = 0; a < 6; ++a)
+#pragma unroll
+    for (int kw = KW0; kw < KW1; ++kw)
+      S[a][kw - KW0] = red[(((a * 2) * 5 + kw) * 4 + j) * 64 + l] +
+                       red[(((a * 2 + 1) * 5 + kw) * 4 + j) * 64 + l];
+#pragma unroll
+  for (int kh = 0; kh < 5; ++kh)
+#pragma unroll
+    for (int kw = KW0; kw < KW1; ++kw) {
+      float sv = 0.f;
+#pragma unroll
+      for (int a = 0; a < 6; ++a)
+        if (wino::kG[a][kh] != 0.f) sv += wino::kG[a][kh] * S[a][kw - KW0];
+      out[(kh * 5 + kw) * 2048] = sv;
+    }
+}
+
+// PROF: per-wave s_memtime stamps at the phase boundaries -> prof[block][wave][6]:
+// start, slices staged, main loop, db2 stripe sums, S_ah stage + barrier,
+// output transform + stores (scripts/wino_lab.py --phases; never used by the
+// executor)
 // Block body (blk): the standalone kernel below, or the filter-gradient role
 // of the merged conv2 backward launch (blk = block index - bwd-data blocks, a
 // multiple of 8: the XCD-aware group mapping is kept)
-constexpr int WF_SMEM_ALL = WF_SMEM > c1f_smem<1, WF_NT / 64>() ? WF_SMEM : c1f_smem<1, WF_NT / 64>();
+constexpr int WF_SMEM_ALL = WF_SMEM + WF_ZR > c1f_smem<1, WF_NT / 64>() ? WF_SMEM + WF_ZR
+                                                                        : c1f_smem<1, WF_NT / 64>();
 // COMPACT: dy2 is the compact dp2 [n][7][7][64] with its argmax codes idx2 (a
 // quarter of the slice loads); the staging expands it into the same dense
 // LDS slices, so everything after it - and every sum - is the dense form's.
 // (Keeping the slices compact in LDS - one value + a 2-bit code per tile, the
 // row transform as a selected kAT coefficient - changed how the compiler
 // contracts the main loop's window transform: part2 differed in the last bit.)
-template <bool PROF, bool COMPACT = false>
+// FORM (mnist.h WGRAD_*, picked per launch by set_wgrad_form): which of the
+// shorter forms the block takes; every form writes the same bits.
+template <bool PROF, bool COMPACT = false, int FORM = 0>
 __device__ __forceinline__ void bwd_filter_wino_block(
     int blk, int batch, const float* __restrict__ a1p, const float* __restrict__ dy2,
     const uint8_t* __restrict__ idx2, float* __restrict__ part2, float* __restrict__ part_db2,
     int nwg, const C1Filter& c1, unsigned long long* __restrict__ prof, float* smem) {
-  unsigned long long stamp[5];
+  unsigned long long stamp[6];
   if constexpr (PROF) stamp[0] = __builtin_amdgcn_s_memtime();
   if (blk >= nwg) {  // conv1 filter-grad role (its dA1 is final)
     conv1_filter_unit<WF_NT, 1>(blk - nwg, batch, c1, smem);
@@ -2047,6 +2151,7 @@ __device__ __forceinline__ void bwd_filter_wino_block(
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int arow = wave % 6, half = wave / 6;
   const int n0 = g * WF_IMG, nimg = min(WF_IMG, batch - n0);
+  constexpr bool BASES = FORM & WGRAD_BASES;
   float* xs = smem;
   float* dys = smem + WF_XS;
   // 1. slices -> LDS (every load issued before the first store)
@@ -2128,6 +2233,9 @@ __device__ __forceinline__ void bwd_filter_wino_block(
         }
       }
     }
+    if constexpr (BASES) {
+      if (tid < WF_ZR) smem[WF_SMEM + tid] = 0.f;
+    }
   }
   __syncthreads();
   if constexpr (PROF) stamp[1] = __builtin_amdgcn_s_memtime();
@@ -2136,12 +2244,12 @@ __device__ __forceinline__ void bwd_filter_wino_block(
 #pragma unroll
   for (int b = 0; b < 6; ++b) acc[b] = f32x4{0.f, 0.f, 0.f, 0.f};
   switch (arow) {
-    case 0: wino_wgrad_row<0>(xs, dys, nimg, lane, half, acc); break;
-    case 1: wino_wgrad_row<1>(xs, dys, nimg, lane, half, acc); break;
-    case 2: wino_wgrad_row<2>(xs, dys, nimg, lane, half, acc); break;
-    case 3: wino_wgrad_row<3>(xs, dys, nimg, lane, half, acc); break;
-    case 4: wino_wgrad_row<4>(xs, dys, nimg, lane, half, acc); break;
-    default: wino_wgrad_row<5>(xs, dys, nimg, lane, half, acc); break;
+    case 0: wino_wgrad_row<0, BASES>(xs, dys, nimg, lane, half, acc); break;
+    case 1: wino_wgrad_row<1, BASES>(xs, dys, nimg, lane, half, acc); break;
+    case 2: wino_wgrad_row<2, BASES>(xs, dys, nimg, lane, half, acc); break;
+    case 3: wino_wgrad_row<3, BASES>(xs, dys, nimg, lane, half, acc); break;
+    case 4: wino_wgrad_row<4, BASES>(xs, dys, nimg, lane, half, acc); break;
+    default: wino_wgrad_row<5, BASES>(xs, dys, nimg, lane, half, acc); break;
   }
   if constexpr (PROF) stamp[2] = __builtin_amdgcn_s_memtime();
   float db = 0.f;  // db2 partial: thread (co, dY row stripe), ci-tile-0 blocks
@@ -2154,6 +2262,7 @@ __device__ __forceinline__ void bwd_filter_wino_block(
     }
   }
   float* dbr = smem + 6 * 2 * 5 * 4 * 64;  // db2 stripes [16][16], after red
+  if constexpr (PROF) stamp[3] = __builtin_amdgcn_s_memtime();
   __syncthreads();  // the slices are reused below
   // 3. S_ah[kw] = sum_b G[b][kw] M_h[a][b]   (this wave's a, h)
   float* red = smem;  // [a][h][kw][j][lane]
@@ -2172,8 +2281,20 @@ __device__ __forceinline__ void bwd_filter_wino_block(
   }
   if (ci_t == 0 && tid < 256) dbr[tid] = db;
   __syncthreads();
-  if constexpr (PROF) stamp[3] = __builtin_amdgcn_s_memtime();
-  if (tid < 256) {  // dW[kh][kw] = sum_a G[a][kh] S_a[kw] for element (j, lane')
+  if constexpr (PROF) stamp[4] = __builtin_amdgcn_s_memtime();
+  if constexpr (FORM & WGRAD_TAIL) {
+    // all 12 waves: thread (element e = (j, lane'), third of the kw columns) -
+    // a column needs only its own S_a[kw], so no LDS word is read twice, and
+    // every dW[kh][kw] keeps the expression below
+    const int e = tid & 255, j = e >> 6, l = e & 63;
+    const int ci = ci_t * 16 + 4 * (l >> 4) + j, co = co_t * 16 + (l & 15);
+    float* out = part2 + (size_t)g * 51200 + ci * 64 + co;
+    switch (wave >> 2) {
+      case 0: wino_wgrad_out<0, 2>(red, j, l, out); break;
+      case 1: wino_wgrad_out<2, 4>(red, j, l, out); break;
+      default: wino_wgrad_out<4, 5>(red, j, l, out); break;
+    }
+  } else if (tid < 256) {  // dW[kh][kw] = sum_a G[a][kh] S_a[kw] for element (j, lane')
 #pragma clang fp contract(off)
     const int j = tid >> 6, l = tid & 63;
     float S[6][5];
@@ -2206,20 +2327,20 @@ __device__ __forceinline__ void bwd_filter_wino_block(
     for (int r = 1; r < 4; ++r) part_db2[(g * 4 + r) * 64 + co] = 0.f;
   }
   if constexpr (PROF) {
-    stamp[4] = __builtin_amdgcn_s_memtime();
+    stamp[5] = __builtin_amdgcn_s_memtime();
     if (lane == 0)
-      for (int k = 0; k < 5; ++k) prof[((size_t)blk * (WF_NT / 64) + wave) * 5 + k] = stamp[k];
+      for (int k = 0; k < 6; ++k) prof[((size_t)blk * (WF_NT / 64) + wave) * 6 + k] = stamp[k];
   }
 }
 
-template <bool PROF, bool COMPACT = false>
+template <bool PROF, bool COMPACT = false, int FORM = 0>
 __global__ __launch_bounds__(WF_NT) void conv2_bwd_filter_wino_kernel(
     int batch, const float* __restrict__ a1p, const float* __restrict__ dy2,
     const uint8_t* __restrict__ idx2, float* __restrict__ part2, float* __restrict__ part_db2,
     int nwg, const C1Filter c1, unsigned long long* __restrict__ prof) {
   __shared__ float smem[WF_SMEM_ALL];
-  bwd_filter_wino_block<PROF, COMPACT>(blockIdx.x, batch, a1p, dy2, idx2, part2, part_db2, nwg, c1,
-                                       prof, smem);
+  bwd_filter_wino_block<PROF, COMPACT, FORM>(blockIdx.x, batch, a1p, dy2, idx2, part2, part_db2,
+                                             nwg, c1, prof, smem);
 }
 
 // Both Winograd conv2 backward products in ONE launch (they depend only on
@@ -2368,7 +2489,7 @@ __device__ void xgmi_fc_gather(const XgmiStepArgs& a, int gb, int ng) {
 
 // COMPACT: dy2 is the compact dp2 with its codes idx2 (both roles); a1 /
 // da1m may be null (bwd_data_wino_block)
-template <bool COMPACT>
+template <bool COMPACT, int FORM>
 __global__ __launch_bounds__(WF_NT) void conv2_bwd_wino_kernel(
     int nd, const float* __restrict__ Ud,
     const float* __restrict__ a1, int batch, float* __restrict__ da1m,
@@ -2401,8 +2522,8 @@ __global__ __launch_bounds__(WF_NT) void conv2_bwd_wino_kernel(
     bwd_data_wino_block<false, false, COMPACT>(b, nd, dy2, idx2, Ud, a1, a1p, batch, da1m, FcSgd{},
                                                c1, nullptr, smem);
   } else {
-    bwd_filter_wino_block<false, COMPACT>(b - nd, batch, a1p, dy2, idx2, part2, part_db2, nwg,
-                                          C1Filter{}, nullptr, smem);
+    bwd_filter_wino_block<false, COMPACT, FORM>(b - nd, batch, a1p, dy2, idx2, part2, part_db2,
+                                                nwg, C1Filter{}, nullptr, smem);
   }
 }
 
@@ -3005,6 +3126,27 @@ size_t part2_floats_wino(int batch) {
   return (size_t)conv2_wino_filter_groups(batch) * (51200 + 256);
 }
 
+// labs / A-B (mnist.h): which forms of the filter-gradient block the three
+// launchers below take
+static int g_wgrad_form = WGRAD_DEFAULT;
+void set_wgrad_form(int mask) {
+  if (mask > WGRAD_DEFAULT) throw std::runtime_error("set_wgrad_form: unknown form bit");
+  g_wgrad_form = mask < 0 ? WGRAD_DEFAULT : mask;
+}
+int wgrad_form() { return g_wgrad_form; }
+// f(std::integral_constant<int, FORM>) for the current mask
+template <typename F>
+static void with_wgrad_form(F&& f) {
+  switch (g_wgrad_form) {
+#define FORM_CASE(M_) case M_: f(std::integral_constant<int, M_>{}); break
+    FORM_CASE(0);
+    FORM_CASE(1);
+    FORM_CASE(2);
+    default: FORM_CASE(3);
+#undef FORM_CASE
+  }
+}
+
 void launch_conv2_bwd_filter_wino(const float* a1p, const float* dy2, int batch, float* part2,
                                   hipStream_t s, const C1FilterArgs* c1, const float* dp2,
                                   const uint8_t* idx2) {
@@ -3012,12 +3154,15 @@ void launch_conv2_bwd_filter_wino(const float* a1p, const float* dy2, int batch,
   const int G = conv2_wino_filter_groups(batch);
   const C1Filter c = c1_args(c1);
   const int n1 = c.part1 ? conv1_filter_blocks(batch, 1) : 0;
-  if (dy2 == nullptr)
-    conv2_bwd_filter_wino_kernel<false, true><<<8 * G + n1, WF_NT, 0, s>>>(
-        batch, a1p, dy, idx2, part2, part2 + (size_t)G * 51200, 8 * G, c, nullptr);
-  else
-    conv2_bwd_filter_wino_kernel<false, false><<<8 * G + n1, WF_NT, 0, s>>>(
-        batch, a1p, dy, idx2, part2, part2 + (size_t)G * 51200, 8 * G, c, nullptr);
+  with_wgrad_form([&](auto form) {
+    constexpr int FORM = decltype(form)::value;
+    if (dy2 == nullptr)
+      conv2_bwd_filter_wino_kernel<false, true, FORM><<<8 * G + n1, WF_NT, 0, s>>>(
+          batch, a1p, dy, idx2, part2, part2 + (size_t)G * 51200, 8 * G, c, nullptr);
+    else
+      conv2_bwd_filter_wino_kernel<false, false, FORM><<<8 * G + n1, WF_NT, 0, s>>>(
+          batch, a1p, dy, idx2, part2, part2 + (size_t)G * 51200, 8 * G, c, nullptr);
+  });
 }
 
 // labs: per-block clock stamps of the merged conv2 backward (null: off)
@@ -3037,14 +3182,17 @@ void launch_conv2_bwd_wino(const float* Ud, const float* a1, const float* a1p, c
     xa = *xfc;
     xgmi_fc_plan(xa, WF_NT, XS_FC_ROLE_BLOCKS);
   }
-  if (dy2 == nullptr)
-    conv2_bwd_wino_kernel<true><<<xa.nfc + nd + 8 * G, WF_NT, 0, s>>>(
-        nd, Ud, a1, batch, da1m, c1_args(c1), a1p, dy, idx2, part2, part2 + (size_t)G * 51200,
-        8 * G, xa, g_c2bw_prof);
-  else
-    conv2_bwd_wino_kernel<false><<<xa.nfc + nd + 8 * G, WF_NT, 0, s>>>(
-        nd, Ud, a1, batch, da1m, c1_args(c1), a1p, dy, idx2, part2, part2 + (size_t)G * 51200,
-        8 * G, xa, g_c2bw_prof);
+  with_wgrad_form([&](auto form) {
+    constexpr int FORM = decltype(form)::value;
+    if (dy2 == nullptr)
+      conv2_bwd_wino_kernel<true, FORM><<<xa.nfc + nd + 8 * G, WF_NT, 0, s>>>(
+          nd, Ud, a1, batch, da1m, c1_args(c1), a1p, dy, idx2, part2, part2 + (size_t)G * 51200,
+          8 * G, xa, g_c2bw_prof);
+    else
+      conv2_bwd_wino_kernel<false, FORM><<<xa.nfc + nd + 8 * G, WF_NT, 0, s>>>(
+          nd, Ud, a1, batch, da1m, c1_args(c1), a1p, dy, idx2, part2, part2 + (size_t)G * 51200,
+          8 * G, xa, g_c2bw_prof);
+  });
 }
 
 void set_conv2_bwd_wino_prof(unsigned long long* p) { g_c2bw_prof = p; }
@@ -3054,12 +3202,15 @@ void launch_conv2_bwd_filter_wino_prof(const float* a1p, const float* dy2, int b
                                        const float* dp2, const uint8_t* idx2) {
   const float* dy = dy2_operand("conv2_bwd_filter_wino_prof", dy2, dp2, idx2);
   const int G = conv2_wino_filter_groups(batch);
-  if (dy2 == nullptr)
-    conv2_bwd_filter_wino_kernel<true, true><<<8 * G, WF_NT, 0, s>>>(
-        batch, a1p, dy, idx2, part2, part2 + (size_t)G * 51200, 8 * G, C1Filter{}, prof);
-  else
-    conv2_bwd_filter_wino_kernel<true, false><<<8 * G, WF_NT, 0, s>>>(
-        batch, a1p, dy, idx2, part2, part2 + (size_t)G * 51200, 8 * G, C1Filter{}, prof);
+  with_wgrad_form([&](auto form) {
+    constexpr int FORM = decltype(form)::value;
+    if (dy2 == nullptr)
+      conv2_bwd_filter_wino_kernel<true, true, FORM><<<8 * G, WF_NT, 0, s>>>(
+          batch, a1p, dy, idx2, part2, part2 + (size_t)G * 51200, 8 * G, C1Filter{}, prof);
+    else
+      conv2_bwd_filter_wino_kernel<true, false, FORM><<<8 * G, WF_NT, 0, s>>>(
+          batch, a1p, dy, idx2, part2, part2 + (size_t)G * 51200, 8 * G, C1Filter{}, prof);
+  });
 }
 
 C1Filter c1_args(const C1FilterArgs* a) {

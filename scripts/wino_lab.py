@@ -21,6 +21,8 @@ def main():
     ap.add_argument("--reps", type=int, default=200)
     ap.add_argument("--only", default="")
     ap.add_argument("--phases", action="store_true", help="per-phase s_memtime of the Winograd wgrad")
+    ap.add_argument("--wgrad-form", type=int, default=-1,
+                    help="set_wgrad_form mask of the Winograd filter gradient (-1: the default forms)")
     a = ap.parse_args()
     dev = torch.device("cuda:0")
     x, y = synthetic_rows("train", 0, 4096)
@@ -32,6 +34,8 @@ def main():
     e.forward_backward_only()
     torch.cuda.synchronize()
     k = native().mnist
+    k.set_wgrad_form(a.wgrad_form)
+    print(f"wgrad form mask {k.wgrad_form()}")
     b, B, lay = e.bufs, e.B, e.layout
     W = lambda n: ptr(e.params) + 4 * lay.offsets[n]  # noqa: E731
     s = stream_handle()
@@ -77,7 +81,7 @@ def main():
         G = k.conv2_wino_filter_groups(B)
         nw = 12
         for form in ("dense", "dp2"):
-            prof = torch.zeros(8 * G * nw * 5, dtype=torch.int64, device=dev)
+            prof = torch.zeros(8 * G * nw * 6, dtype=torch.int64, device=dev)
             for _ in range(5):
                 if form == "dense":
                     k.conv2_bwd_filter_wino_prof(ptr(b["a1pf"]), ptr(b["dy2"]), B, ptr(b["part2"]),
@@ -86,14 +90,24 @@ def main():
                     k.conv2_bwd_filter_wino_dp2(ptr(b["a1pf"]), ptr(dp2), ptr(b["idx2"]), B,
                                                 ptr(b["part2"]), s, ptr(prof))
             torch.cuda.synchronize()
-            t = prof.view(8 * G, nw, 5).double()
+            t = prof.view(8 * G, nw, 6).double()
             t0 = t[..., 0].min()
             d = t[..., 1:] - t[..., :-1]
-            names = ["staging", "main loop", "db + S_a", "dW + stores"]
+            names = ["staging", "main loop", "db2 sums", "S_a + barrier", "dW + stores"]
             print(f"wgrad(wino, {form}) phases, cycles per wave: mean / max")
             for i, nm in enumerate(names):
-                print(f"  {nm:12s} {d[..., i].mean().item():9.0f} {d[..., i].max().item():9.0f}")
-            print(f"  span (first start -> last end) {(t[..., 4].max() - t0).item():.0f} cycles; "
+                print(f"  {nm:14s} {d[..., i].mean().item():9.0f} {d[..., i].max().item():9.0f}")
+            # a block is as long as its slowest wave: first start -> last end per block
+            blk = t[..., 5].max(dim=1).values - t[..., 0].min(dim=1).values
+            ml = t[..., 2].max(dim=1).values - t[..., 1].min(dim=1).values
+            tail = t[..., 5].max(dim=1).values - t[..., 2].max(dim=1).values
+            bid = torch.arange(8 * G, device=dev)
+            db2 = (((bid >> 3) if G % 8 == 0 else bid) & 1) == 0  # the ci-tile-0 blocks sum db2
+            for nm, v in (("block", blk), ("main loop, first in -> last out", ml),
+                          ("tail, last out of the loop -> end", tail)):
+                print(f"  {nm}: mean {v.mean().item():.0f}, db2 blocks {v[db2].mean().item():.0f}, "
+                      f"the others {v[~db2].mean().item():.0f}")
+            print(f"  span (first start -> last end) {(t[..., 5].max() - t0).item():.0f} cycles; "
                   f"block start spread {(t[..., 0].max() - t0).item():.0f}")
     if a.phases:
         nb, nw = B * 4, 8
