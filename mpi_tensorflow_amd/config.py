@@ -198,6 +198,50 @@ def parse_ema(spec: str):
     return float(decay), int(K)
 
 
+MAX_MIX = 50.0  # percent: the largest share --mix gives the partner row
+MIX_KINDS = ("mixup", "cutmix")
+
+
+def parse_mix(spec: str):
+    """`mixup:M` or `cutmix:M` (exactly one; M a float in percent, 0 < M <= 50:
+    the largest share of the partner row) -> (kind, M); the definition:
+    docs/ACCURACY.md."""
+    if not isinstance(spec, str) or not spec.strip():
+        raise ValueError("empty mix spec; expected e.g. 'mixup:50', 'cutmix:25'")
+    seen = {}
+    for item in spec.split(","):
+        name, sep, val = item.strip().partition(":")
+        try:
+            if name not in MIX_KINDS or not sep:
+                raise ValueError
+            v = float(val)
+            if v != v or abs(v) == float("inf"):
+                raise ValueError
+        except ValueError:
+            raise ValueError(f"bad item {item!r} in mix spec {spec!r}; expected mixup:M or "
+                             f"cutmix:M") from None
+        if name in seen:
+            raise ValueError(f"mix spec {spec!r} names {name!r} twice")
+        seen[name] = v
+    if len(seen) != 1:
+        raise ValueError(f"mix spec {spec!r} names both mixup and cutmix; a run mixes one way")
+    (kind, M), = seen.items()
+    if not 0.0 < M <= MAX_MIX:
+        raise ValueError(f"mix {kind} must be in (0, {MAX_MIX:g}] percent, got {M:g}")
+    return kind, float(M)
+
+
+def check_label_smoothing(eps) -> float:
+    """--label-smoothing EPS: a float with 0 <= EPS < 1."""
+    try:
+        v = float(eps)
+    except (TypeError, ValueError):
+        raise ValueError(f"label smoothing must be a float, got {eps!r}") from None
+    if not 0.0 <= v < 1.0:  # (false for nan)
+        raise ValueError(f"label smoothing must be in [0, 1), got {v:g}")
+    return v
+
+
 @dataclasses.dataclass
 class TrainConfig:
     """Every knob of a training run.  Defaults = the reference's behaviour
@@ -264,6 +308,13 @@ class TrainConfig:
     # every K-th step (parse_ema: DECAY[,every:K]), evaluated at every logged
     # eval event, saved with the checkpoints; None = no average is kept
     ema: Optional[str] = None
+    # soft training targets (docs/ACCURACY.md): label smoothing EPS, the target
+    # (1 - EPS) onehot + EPS / classes; 0 = the hard label, nothing extra runs
+    label_smoothing: float = 0.0
+    # mixup:M / cutmix:M (parse_mix): every training row blended with, or given
+    # a box of, a partner row of its pass, redrawn each pass on the device; the
+    # target is the same blend of the two labels; None = rows stay apart
+    mix: Optional[str] = None
     # learning rate / optimiser
     base_lr: float = BASE_LR
     lr_decay: float = LR_DECAY
@@ -350,6 +401,9 @@ class TrainConfig:
                 raise ValueError("--ema does not support --model resnet18 (its forward lives in "
                                  "the autograd engine, and its BatchNorm statistics would need "
                                  "averaging too); use mnist_cnn or lenet5")
+        self.label_smoothing = check_label_smoothing(self.label_smoothing)
+        if self.mix is not None:
+            parse_mix(self.mix)
         if self.predict_weights is not None and self.predict_weights not in PREDICT_WEIGHTS:
             raise ValueError(f"unknown predict weights {self.predict_weights!r}; choose from "
                              f"{PREDICT_WEIGHTS}")
@@ -370,6 +424,9 @@ class TrainConfig:
         return self
 
     def _validate_predict(self) -> None:
+        if self.mix is not None or self.label_smoothing > 0.0:
+            raise ValueError("--predict: mix and label smoothing are training-only (--mix, "
+                             "--label-smoothing); a prediction has no target to soften")
         if not self.resume:
             raise ValueError("--predict needs the checkpoint to predict with: --resume PATH")
         if self.model == "resnet18":
@@ -473,6 +530,14 @@ def build_arg_parser(prog: str = "mpipy.py") -> argparse.ArgumentParser:
                         "DECAY[,every:K] (0 < DECAY < 1, updated after every K-th step with TF's "
                         "num_updates warm-up); evaluated at every logged eval event, saved with "
                         "the checkpoints (mnist_cnn, lenet5)")
+    p.add_argument("--label-smoothing", type=float, default=d.label_smoothing, metavar="EPS",
+                   help="train against (1 - EPS) onehot + EPS / classes, 0 <= EPS < 1 (0: the "
+                        "hard label, the default); evaluation is untouched")
+    p.add_argument("--mix", default=d.mix, metavar="SPEC",
+                   help="mixup:M or cutmix:M (0 < M <= 50 percent, the largest share of the "
+                        "partner row): every training row is blended with (mixup), or gets a box "
+                        "of (cutmix), another row of its pass, redrawn each pass on the device; "
+                        "the target blends the two labels alike (mixup:50 is the usual mixup)")
     p.add_argument("--base-lr", type=float, default=d.base_lr)
     p.add_argument("--lr-decay", type=float, default=d.lr_decay)
     p.add_argument("--momentum", type=float, default=d.momentum)

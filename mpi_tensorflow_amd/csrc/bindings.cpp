@@ -309,6 +309,27 @@ PYBIND11_MODULE(_C, m) {
         py::arg("rank"), py::arg("base_lr"), py::arg("decay"), py::arg("hd"), py::arg("dh"),
         py::arg("dlog"), py::arg("loss_rows"), py::arg("lr_out"), py::arg("correct"), py::arg("s"),
         py::arg("dh16"), py::arg("dht16"), py::arg("splits"), py::arg("lbatch"));
+  // ... against a soft target (labels2 / lam may be 0: lam = 1); always the soft kernel
+  k.def("fc_head_train_soft",
+        [](uintptr_t part, uintptr_t b3, uintptr_t w4, uintptr_t b4, uintptr_t labels, int n_local,
+           uintptr_t step, int batch, float keep, uint32_t seed, uint32_t rank, float base_lr,
+           float decay, uintptr_t hd, uintptr_t dh, uintptr_t dlog, uintptr_t loss_rows,
+           uintptr_t lr_out, uintptr_t correct, uintptr_t s, uintptr_t dh16, uintptr_t dht16,
+           int splits, int lbatch, uintptr_t labels2, uintptr_t lam, float eps) {
+          mnist::launch_fc_head_train_soft(
+              P<const float>(part), P<const float>(b3), P<const float>(w4), P<const float>(b4),
+              P<const int>(labels), n_local, P<const long long>(step), batch, keep, seed, rank,
+              base_lr, decay, P<float>(hd), P<float>(dh), P<float>(dlog), P<float>(loss_rows),
+              P<float>(lr_out), P<int>(correct), S(s), P<uint16_t>(dh16), P<uint16_t>(dht16),
+              splits, lbatch, P<const int>(labels2), P<const float>(lam), eps);
+          check_launch();
+        },
+        py::arg("part"), py::arg("b3"), py::arg("w4"), py::arg("b4"), py::arg("labels"),
+        py::arg("n_local"), py::arg("step"), py::arg("batch"), py::arg("keep"), py::arg("seed"),
+        py::arg("rank"), py::arg("base_lr"), py::arg("decay"), py::arg("hd"), py::arg("dh"),
+        py::arg("dlog"), py::arg("loss_rows"), py::arg("lr_out"), py::arg("correct"), py::arg("s"),
+        py::arg("dh16"), py::arg("dht16"), py::arg("splits"), py::arg("lbatch"),
+        py::arg("labels2"), py::arg("lam"), py::arg("eps"));
   k.def("set_conv2_bwd_prof_bf16", [](uintptr_t p) {
     mnist16::set_conv2_bwd_prof(reinterpret_cast<unsigned long long*>(p));
   });
@@ -781,6 +802,22 @@ PYBIND11_MODULE(_C, m) {
   }, py::arg("data"), py::arg("labels"), py::arg("step"), py::arg("n_local"), py::arg("batch"),
      py::arg("row_elems"), py::arg("xb"), py::arg("yb"), py::arg("st"), py::arg("lr_base") = 0.f,
      py::arg("lr_decay") = 1.f, py::arg("lr_out") = 0);
+  g.def("gather_soft", [](uintptr_t labels2, uintptr_t lam, uintptr_t step, int n_local, int batch,
+                          uintptr_t y2b, uintptr_t lamb, uintptr_t st) {
+    gops::gather_soft(P<const int>(labels2), P<const float>(lam), P<const long long>(step), n_local,
+                      batch, P<int>(y2b), P<float>(lamb), S(st));
+    check_launch();
+  });
+  g.def("xent_mean_soft", [](uintptr_t logits, uintptr_t labels, uintptr_t labels2, uintptr_t lam,
+                             float eps, int B, int C, uintptr_t loss_rows, uintptr_t dlogits,
+                             uintptr_t mean, uintptr_t correct, uintptr_t st) {
+    gops::xent_mean_soft(P<const float>(logits), P<const int>(labels), P<const int>(labels2),
+                         P<const float>(lam), eps, B, C, P<float>(loss_rows), P<float>(dlogits),
+                         P<float>(mean), P<int>(correct), S(st));
+    check_launch();
+  }, py::arg("logits"), py::arg("labels"), py::arg("labels2"), py::arg("lam"), py::arg("eps"),
+     py::arg("B"), py::arg("C"), py::arg("loss_rows"), py::arg("dlogits"), py::arg("mean"),
+     py::arg("correct"), py::arg("st"));
   // per-pass row shuffle of the device-resident shard (kernels/shuffle.h)
   g.def("shuffle_rows", [](uintptr_t src_x, uintptr_t src_y, uintptr_t dst_x, uintptr_t dst_y,
                            long long n, long long row_elems, uint32_t key, uintptr_t st) {
@@ -815,6 +852,17 @@ PYBIND11_MODULE(_C, m) {
      py::arg("H"), py::arg("W"), py::arg("C"), py::arg("use_perm"), py::arg("perm_key"),
      py::arg("aug_key"), py::arg("K"), py::arg("flip"), py::arg("fill"), py::arg("tables"),
      py::arg("S"), py::arg("st"));
+  // mixup / cutmix of a loaded pass (table: 3 x 129 device int32, rng.mix_table)
+  g.def("mix_rows", [](uintptr_t src_x, uintptr_t src_y, uintptr_t dst_x, uintptr_t dst_y,
+                       uintptr_t dst_y2, uintptr_t dst_lam, long long n, int H, int W, int C,
+                       bool cutmix, uint32_t mix_key, uintptr_t table, uintptr_t st) {
+    augment::mix_rows(P<const float>(src_x), P<const int>(src_y), P<float>(dst_x), P<int>(dst_y),
+                      P<int>(dst_y2), P<float>(dst_lam), n, H, W, C, cutmix, mix_key,
+                      P<const int>(table), S(st));
+    check_launch();
+  }, py::arg("src_x"), py::arg("src_y"), py::arg("dst_x"), py::arg("dst_y"), py::arg("dst_y2"),
+     py::arg("dst_lam"), py::arg("n"), py::arg("H"), py::arg("W"), py::arg("C"),
+     py::arg("cutmix"), py::arg("mix_key"), py::arg("table"), py::arg("st"));
   // inference (kernels/predict.h): one view of the input rows, the prediction head
   g.def("predict_prep", [](uintptr_t src, bool src_u8, uintptr_t dst, long long n, int H, int W,
                            int C, int dy, int dx, bool flip, float fill, uintptr_t lut,
@@ -839,7 +887,8 @@ PYBIND11_MODULE(_C, m) {
   py::class_<MnistPtrs>(m, "MnistPtrs")
       .def(py::init<>())
 #define RW(f) .def_readwrite(#f, &MnistPtrs::f)
-          RW(train_x) RW(train_y) RW(n_local) RW(batch) RW(params) RW(grads) RW(mom) RW(total)
+          RW(train_x) RW(train_y) RW(train_y2) RW(train_lam) RW(label_smoothing)
+          RW(n_local) RW(batch) RW(params) RW(grads) RW(mom) RW(total)
               RW(l2_end) RW(bucket1) RW(off_w4) RW(off_b4) RW(off_w3) RW(off_b3) RW(off_w2)
                   RW(off_b2) RW(off_w1) RW(off_b1) RW(step) RW(lr) RW(correct) RW(a1) RW(idx1)
                       RW(a2) RW(idx2) RW(fc1_part) RW(hd) RW(dh) RW(dlog) RW(loss_rows) RW(dy2)
@@ -982,7 +1031,8 @@ PYBIND11_MODULE(_C, m) {
   py::class_<LenetPtrs>(m, "LenetPtrs")
       .def(py::init<>())
 #define RWL(f) .def_readwrite(#f, &LenetPtrs::f)
-          RWL(train_x) RWL(train_y) RWL(n_local) RWL(batch) RWL(params) RWL(grads) RWL(mom)
+          RWL(train_x) RWL(train_y) RWL(train_y2) RWL(train_lam) RWL(label_smoothing)
+          RWL(n_local) RWL(batch) RWL(params) RWL(grads) RWL(mom)
               RWL(total) RWL(off) RWL(step) RWL(lr) RWL(correct) RWL(acts) RWL(deltas) RWL(convp)
                   RWL(loss_rows) RWL(base_lr) RWL(lr_decay) RWL(momentum) RWL(grad_bf16) RWL(gb16)
                   RWL(xrecv) RWL(xgrads2) RWL(xdone);

@@ -44,4 +44,22 @@ void affine_rows(const float* src_x, const int* src_y, float* dst_x, int* dst_y,
                  int H, int W, int C, bool use_perm, uint32_t perm_key, uint32_t aug_key, int K,
                  bool flip, float fill, const int* tables, int S, hipStream_t st);
 
+// mixup / cutmix of a loaded pass (--mix): dst row i = src row i blended with
+// its partner row j of the same pass.  The draw of row i (rng.mix_params):
+//   g0 = mix32(mix_key ^ i), g1 = mix32(g0 + GOLDEN), g2 = mix32(g1 + GOLDEN)
+//   level = g0 % 129 into `table` = wq | bh | bw, 3 x 129 device int32 (rng.mix_table)
+//   j = perm(i) of shuffle.h under the key mix32(mix_key ^ GOLDEN)
+//   cy = g1 % (H - bh + 1), cx = g2 % (W - bw + 1)
+//   lam = (65536 - wq) 2^-16, w = wq 2^-16
+//   mixup:  dst = lam src[i] + w src[j], each product and the sum one rounded
+//           fp32 operation (no fused multiply-add)
+//   cutmix: dst = src[j] for cy <= y < cy + bh, cx <= x < cx + bw, src[i] elsewhere
+//   dst_y[i] = src_y[i], dst_y2[i] = src_y[j], dst_lam[i] = lam
+// Identical to utils/rng.py mix_np, bit for bit.  H, W <= 1024.  Rows of dst at n
+// and above and all of src are not written.  One launch, no allocation, no
+// sync: capturable into a hipGraph.
+void mix_rows(const float* src_x, const int* src_y, float* dst_x, int* dst_y, int* dst_y2,
+              float* dst_lam, long long n, int H, int W, int C, bool cutmix, uint32_t mix_key,
+              const int* table, hipStream_t st);
+
 }  // namespace augment

@@ -18,6 +18,9 @@
 // affine_rows (rotate / scale / cutout) keeps that shape; the seven hashes, the
 // table reads and the Q16 matrix are per row and scalar as well, and each
 // destination float is four guarded single loads and seven fp32 operations.
+//
+// mix_rows (mixup / cutmix) keeps that shape too: it blends the rows of one
+// loaded pass with partner rows of the same pass.
 #include "augment.h"
 
 #include <algorithm>
@@ -248,6 +251,96 @@ __global__ __launch_bounds__(THREADS) void affine_kernel(const float* __restrict
   }
 }
 
+// ---- mixup / cutmix (--mix): blend the rows of a pass with partner rows ----
+// The draw of working row i in scalar registers, as above: three hashes, the
+// level's table entries, the Feistel walk to the partner j and the box corner.
+// mixup: lam a + w b, each product and the sum one rounded fp32 operation;
+// cutmix: b inside the box, a elsewhere.  Both rows are read as whole vectors
+// (rows of one pass: the partner's lines are some other workgroup's own lines).
+struct MixGeo {
+  uint32_t H, W, C, wc;
+  uint32_t m_wc, m_c;
+  uint32_t key;
+  int cutmix;
+};
+
+template <int U>
+__global__ __launch_bounds__(THREADS) void mix_kernel(
+    const float* __restrict__ src_x, const int* __restrict__ src_y, float* __restrict__ dst_x,
+    int* __restrict__ dst_y, int* __restrict__ dst_y2, float* __restrict__ dst_lam,
+    shuffle::Perm p, MixGeo g, const int* __restrict__ tab, long long row_vecs) {
+#pragma clang fp contract(off)  // every * and + below is one rounded fp32 operation
+  const long long v0 = (long long)blockIdx.y * PIECE + threadIdx.x;
+  const long long row_elems = row_vecs * U;
+  const long long n = p.n;
+  for (long long i = blockIdx.x; i < n; i += gridDim.x) {
+    const uint32_t g0 = mix32(g.key ^ (uint32_t)i), g1 = mix32(g0 + 0x9E3779B9u),
+                   g2 = mix32(g1 + 0x9E3779B9u);
+    const uint32_t level = g0 % LEVELS;
+    const int wq = tab[level];
+    const uint32_t bh = (uint32_t)tab[LEVELS + level], bw = (uint32_t)tab[2 * LEVELS + level];
+    const uint32_t j = shuffle::perm_of(p, (uint32_t)i);
+    const uint32_t cy = g1 % (g.H - bh + 1u), cx = g2 % (g.W - bw + 1u);
+    const float lam = (float)(65536 - wq) * 0x1p-16f, w = (float)wq * 0x1p-16f;
+    const float* a = src_x + i * row_elems;
+    const float* b = src_x + (long long)j * row_elems;
+    float* d = dst_x + i * row_elems;
+    float o[PER_THREAD][U];
+#pragma unroll
+    for (int u = 0; u < PER_THREAD; ++u) {
+      const long long v = v0 + u * THREADS;
+      if (v < row_vecs) {
+        float va[U], vb[U];
+        if constexpr (U == 4) {
+          const f32x4 ta = reinterpret_cast<const f32x4*>(a)[v];
+          const f32x4 tb = reinterpret_cast<const f32x4*>(b)[v];
+#pragma unroll
+          for (int k = 0; k < 4; ++k) va[k] = ta[k], vb[k] = tb[k];
+        } else {
+          va[0] = a[v], vb[0] = b[v];
+        }
+        if (g.cutmix) {
+          const uint32_t e = (uint32_t)(v * U);
+          uint32_t y = div_by(e, g.wc, g.m_wc);
+          uint32_t x = div_by(e - y * g.wc, g.C, g.m_c);
+          uint32_t c = e - y * g.wc - x * g.C;
+#pragma unroll
+          for (int k = 0; k < U; ++k) {
+            o[u][k] = (y - cy < bh && x - cx < bw) ? vb[k] : va[k];
+            if (++c == g.C) {
+              c = 0;
+              if (++x == g.W) x = 0, ++y;
+            }
+          }
+        } else {
+#pragma unroll
+          for (int k = 0; k < U; ++k) {
+            const float pa = lam * va[k], pb = w * vb[k];
+            o[u][k] = pa + pb;
+          }
+        }
+      }
+    }
+#pragma unroll
+    for (int u = 0; u < PER_THREAD; ++u) {
+      const long long v = v0 + u * THREADS;
+      if (v < row_vecs) {
+        if constexpr (U == 4) {
+          const f32x4 t = {o[u][0], o[u][1], o[u][2], o[u][3]};
+          reinterpret_cast<f32x4*>(d)[v] = t;
+        } else {
+          d[v] = o[u][0];
+        }
+      }
+    }
+    if (blockIdx.y == 0 && threadIdx.x == 0) {
+      dst_y[i] = src_y[i];
+      dst_y2[i] = src_y[j];
+      dst_lam[i] = lam;
+    }
+  }
+}
+
 // the grid of both kernels: (rows in flight, 16 KB pieces of a row)
 dim3 rows_grid(const char* who, long long n, long long row_vecs) {
   const long long pieces = (row_vecs + PIECE - 1) / PIECE;
@@ -275,6 +368,11 @@ void launch_affine(const float* src_x, const int* src_y, float* dst_x, int* dst_
 bool overlap(const void* a, const void* b, unsigned long long bytes) {
   const uintptr_t x = reinterpret_cast<uintptr_t>(a), y = reinterpret_cast<uintptr_t>(b);
   return x < y + bytes && y < x + bytes;
+}
+
+bool range_overlap(const void* a, unsigned long long na, const void* b, unsigned long long nb) {
+  const uintptr_t x = reinterpret_cast<uintptr_t>(a), y = reinterpret_cast<uintptr_t>(b);
+  return x < y + nb && y < x + na;
 }
 
 // The checks both entries share, thrown before anything is launched; false: nothing to do.
@@ -340,6 +438,39 @@ void affine_rows(const float* src_x, const int* src_y, float* dst_x, int* dst_y,
     launch_affine<4>(src_x, src_y, dst_x, dst_y, p, use_perm, g, tables, S, row_elems / 4, st);
   else
     launch_affine<1>(src_x, src_y, dst_x, dst_y, p, use_perm, g, tables, S, row_elems, st);
+}
+
+void mix_rows(const float* src_x, const int* src_y, float* dst_x, int* dst_y, int* dst_y2,
+              float* dst_lam, long long n, int H, int W, int C, bool cutmix, uint32_t mix_key,
+              const int* table, hipStream_t st) {
+  if (H > MAX_SIDE || W > MAX_SIDE) throw std::runtime_error("mix_rows: H, W above 1024");
+  if (!table || !src_y || !dst_y || !dst_y2 || !dst_lam)
+    throw std::runtime_error("mix_rows: null buffer");
+  if (!check_rows("mix_rows", src_x, src_y, dst_x, dst_y, n, H, W, C, 0)) return;
+  // every output against every input and against the other outputs (4-byte rows of n)
+  const unsigned long long yb = (unsigned long long)n * sizeof(int);
+  const unsigned long long xb = (unsigned long long)n * H * W * C * sizeof(float);
+  const void* small[4] = {src_y, dst_y, dst_y2, dst_lam};
+  for (int a = 0; a < 4; ++a) {
+    for (int b = a + 1; b < 4; ++b)
+      if (overlap(small[a], small[b], yb)) throw std::runtime_error("mix_rows: src and dst overlap");
+    if (a > 0 && (range_overlap(small[a], yb, src_x, xb) ||
+                  range_overlap(small[a], yb, dst_x, xb)))
+      throw std::runtime_error("mix_rows: src and dst overlap");
+  }
+  const long long row_elems = (long long)H * W * C;
+  // the partner permutation has a key of its own, derived from the pass's
+  const shuffle::Perm p = shuffle::make_perm(mix32(mix_key ^ 0x9E3779B9u), n);
+  MixGeo g;
+  g.H = H, g.W = W, g.C = C, g.wc = (uint32_t)W * C;
+  g.m_wc = magic(g.wc), g.m_c = magic(g.C);
+  g.key = mix_key, g.cutmix = cutmix ? 1 : 0;
+  if (vector_rows(src_x, dst_x, row_elems))
+    mix_kernel<4><<<rows_grid("mix_rows", n, row_elems / 4), THREADS, 0, st>>>(
+        src_x, src_y, dst_x, dst_y, dst_y2, dst_lam, p, g, table, row_elems / 4);
+  else
+    mix_kernel<1><<<rows_grid("mix_rows", n, row_elems), THREADS, 0, st>>>(
+        src_x, src_y, dst_x, dst_y, dst_y2, dst_lam, p, g, table, row_elems);
 }
 
 }  // namespace augment

@@ -39,6 +39,12 @@ struct ImageArgs {
   int* errors;      // wrong-prediction counter
   float* logits;    // optional [rows][10]
   int stop_phase = 99;  // profiling: return after this phase
+  // train against a soft target (--mix, --label-smoothing; docs/ACCURACY.md):
+  // partner labels and own-label shares of the rows of y (null: lam = 1), and
+  // the smoothing.  eps > 0 or lam set takes the kernel's SOFT instantiation
+  const int* y2 = nullptr;
+  const float* lam = nullptr;
+  float eps = 0.f;
 };
 
 // one workgroup per image: forward (conv1+ReLU+pool, conv2+ReLU+pool, FC chain,

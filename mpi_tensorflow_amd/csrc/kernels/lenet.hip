@@ -95,7 +95,8 @@ __device__ __forceinline__ void pool4(f2 a01, f2 a23, float& v, int& q) {
 // in flight across them)
 // one workgroup per CU (LDS): 2 waves a SIMD, up to 256 VGPRs a lane - the room
 // the FC weight prefetches live in
-template <bool TRAIN>
+// SOFT (train): the xent wave forms the soft target of ImageArgs y2 / lam / eps
+template <bool TRAIN, bool SOFT = false>
 __global__ __launch_bounds__(NT, 1) void image_kernel(const ImageArgs a) {
   __shared__ float sm[S_TOTAL];
   __shared__ uint8_t q1s[P1 * P1 * C1];
@@ -392,8 +393,18 @@ __global__ __launch_bounds__(NT, 1) void image_kernel(const ImageArgs a) {
     }
     const float e = tid < F3 ? __expf(lg - mx) : 0.f;
     const float se = wave_sum(e);
-    const float lab = wave_sum(tid == label ? lg : 0.f);
-    if (tid < F3) sm[S_D3 + tid] = (e / se - (tid == label ? 1.f : 0.f)) / (float)a.batch;
+    float lab;
+    if constexpr (SOFT) {  // t = (1 - eps) (lam [c == y1] + (1 - lam) [c == y2]) + eps / classes
+      const int label2 = a.lam ? a.y2[row] : label;
+      const float lam = a.lam ? a.lam[row] : 1.f;
+      const float av = (tid == label ? lam : 0.f) + (tid == label2 ? 1.f - lam : 0.f);
+      const float t = (1.f - a.eps) * av + a.eps / (float)F3;
+      lab = wave_sum(tid < F3 ? t * lg : 0.f);  // sum t z
+      if (tid < F3) sm[S_D3 + tid] = (e / se - t) / (float)a.batch;
+    } else {
+      lab = wave_sum(tid == label ? lg : 0.f);
+      if (tid < F3) sm[S_D3 + tid] = (e / se - (tid == label ? 1.f : 0.f)) / (float)a.batch;
+    }
     if (tid == 0 && q == 0) {
       a.loss_rows[img] = logf(se) + mx - lab;
       if (a.correct && am == label) atomicAdd(a.correct, 1);
@@ -909,7 +920,12 @@ __global__ __launch_bounds__(256) void update_push_kernel(
 void launch_image_train(const ImageArgs& a, hipStream_t s) {
   if (a.batch <= 0 || a.n_local <= a.batch)
     throw std::runtime_error("lenet: the local shard must exceed the batch");
-  image_kernel<true><<<a.batch * PARTS, NT, 0, s>>>(a);
+  if (a.lam && !a.y2) throw std::runtime_error("lenet: lam without y2");
+  if (!(a.eps >= 0.f && a.eps < 1.f)) throw std::runtime_error("lenet: eps not in [0, 1)");
+  if (a.eps > 0.f || a.lam)
+    image_kernel<true, true><<<a.batch * PARTS, NT, 0, s>>>(a);
+  else
+    image_kernel<true><<<a.batch * PARTS, NT, 0, s>>>(a);
 }
 
 void launch_image_eval(const ImageArgs& a, int rows, hipStream_t s) {

@@ -134,7 +134,22 @@ void launch_fc_head_train(const float* part, const float* b3, const float* w4, c
                           float lr_decay, float* hd, float* dh, float* dlog, float* loss_rows,
                           float* lr_out, int* correct, hipStream_t s, uint16_t* dh16 = nullptr,
                           uint16_t* dht16 = nullptr, int splits = 14,  // slabs in part
-                          int lbatch = 0);
+                          int lbatch = 0,
+                          // a soft target (--mix, --label-smoothing; docs/ACCURACY.md): the
+                          // partner labels and the own label's share of every shard row, and
+                          // the smoothing.  lam null: lam = 1.  eps > 0 or lam set takes
+                          // launch_fc_head_train_soft; otherwise the hard-label launches
+                          const int* labels2 = nullptr, const float* lam = nullptr,
+                          float eps = 0.f);
+// The soft-target head whatever the arguments (eps = 0, lam null: the hard
+// head's bits); one kernel for both forms of FC_CHAIN_HEAD.
+void launch_fc_head_train_soft(const float* part, const float* b3, const float* w4,
+                               const float* b4, const int* labels, int n_local,
+                               const long long* step, int batch, float keep_prob, uint32_t seed,
+                               uint32_t rank, float base_lr, float lr_decay, float* hd, float* dh,
+                               float* dlog, float* loss_rows, float* lr_out, int* correct,
+                               hipStream_t s, uint16_t* dh16, uint16_t* dht16, int splits,
+                               int lbatch, const int* labels2, const float* lam, float eps);
 // A/B of the shorter FC-chain forms (mnist.hip): a mask of the forms the
 // launchers take; the older form of each stays selectable on the same build.
 // mask < 0: back to the default.  Not captured: a graph keeps what it recorded.

@@ -254,7 +254,6 @@ __global__ __launch_bounds__(64 * WM * WN * WK) void fc1_fwd_kernel(
 // waves take consecutive quarters of the split (49 k-steps each, every load
 // issued up front, two accumulator chains) and meet once in LDS; wave 0
 // writes the split's partial slab part[split][row][512] (the head sums them).
-constexpr int FC1T_SPLITS = 8;
 constexpr int FC1T_KW = FC1_IN / FC1T_SPLITS / 4;  // 98 features per wave
 static_assert(FC1T_KW % 2 == 0 && FC1_IN % (FC1T_SPLITS * 4) == 0, "fc1_fwd_t split");
 
@@ -2948,7 +2947,14 @@ void launch_fc_head_train(const float* part, const float* b3, const float* w4, c
                           float keep_prob, uint32_t seed, uint32_t rank, float base_lr,
                           float lr_decay, float* hd, float* dh, float* dlog, float* loss_rows,
                           float* lr_out, int* correct, hipStream_t s, uint16_t* dh16,
-                          uint16_t* dht16, int splits, int lbatch) {
+                          uint16_t* dht16, int splits, int lbatch, const int* labels2,
+                          const float* lam, float eps) {
+  if (eps > 0.f || lam) {  // a soft target (mnist_head_soft.hip); the launches below are untouched
+    launch_fc_head_train_soft(part, b3, w4, b4, labels, n_local, step, batch, keep_prob, seed,
+                              rank, base_lr, lr_decay, hd, dh, dlog, loss_rows, lr_out, correct, s,
+                              dh16, dht16, splits, lbatch, labels2, lam, eps);
+    return;
+  }
   if (lbatch < 0 || lbatch > batch) throw std::runtime_error("fc_head_train: lbatch > batch");
 #define HEAD(K_, NS_, GRID_)                                                                   \
   K_<NS_><<<GRID_, 256, 0, s>>>(part, b3, w4, b4, labels, n_local, step, batch, keep_prob, seed, \

@@ -8,6 +8,7 @@ namespace mnist {
 
 constexpr int FC1_IN = 3136, FC1_OUT = 512, NCLS = 10;
 constexpr int FC1_SPLITS = 14;  // train fc1 split-K slabs
+constexpr int FC1T_SPLITS = 8;  // ... of the feature-major fc1 forward (mnist.hip fc1_fwd_t_kernel)
 constexpr int SMALL_BLOCKS = 8;  // blocks of the fc2 / bias grads role in fc1 backward
 
 // reference batch offset (step * B) % (N_local - B) (/root/reference/mpipy.py:80)

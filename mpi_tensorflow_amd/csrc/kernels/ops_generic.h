@@ -279,6 +279,12 @@ void stem_wgrad(const float* gpad, int R, int sc, int seg, int K, float* gw, hip
 // one-workgroup softmax xent with the mean loss (B rows of C classes)
 void xent_mean(const float* logits, const int* labels, int B, int C, float* loss_rows,
                float* dlogits, float* mean, int* correct, hipStream_t st);
+// ... against a soft target (docs/ACCURACY.md): t = (1 - eps) (lam [c == y1] +
+// (1 - lam) [c == y2]) + eps / C; labels2 / lam null: lam = 1.  eps = 0, lam = 1:
+// xent_mean's bits
+void xent_mean_soft(const float* logits, const int* labels, const int* labels2, const float* lam,
+                    float eps, int B, int C, float* loss_rows, float* dlogits, float* mean,
+                    int* correct, hipStream_t st);
 // small FC layers: y = x W (+ b) (+ ReLU); backward dW, db, dX (dX optional)
 void linear_fwd(const float* x, const float* w, const float* b, float* y, int M, int K, int N,
                 bool relu, hipStream_t st);
@@ -290,5 +296,8 @@ void lr_from_step(const long long* step, int n_local, int batch, float base, flo
 void gather_batch(const float* data, const int* labels, const long long* step, int n_local,
                   int batch, long long row_elems, float* xb, int* yb, hipStream_t st,
                   float lr_base = 0.f, float lr_decay = 1.f, float* lr_out = nullptr);
+// y2b / lamb = labels2 / lam of the rows gather_batch reads at this step (--mix)
+void gather_soft(const int* labels2, const float* lam, const long long* step, int n_local,
+                 int batch, int* y2b, float* lamb, hipStream_t st);
 
 }  // namespace gops

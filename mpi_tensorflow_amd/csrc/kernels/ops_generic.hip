@@ -765,6 +765,55 @@ __global__ __launch_bounds__(256) void xent_mean_kernel(const float* __restrict_
   if (threadIdx.x == 0) mean_out[0] = (part[0] + part[1] + part[2] + part[3]) / (float)B;
 }
 
+// The same against a soft target (--label-smoothing, --mix): per class
+// t = (1 - eps) (lam [c == y1] + (1 - lam) [c == y2]) + eps / C, loss =
+// logsumexp - sum t z, dlogits = (p - t) / B; the hit count stays argmax
+// against y1.  labels2 / lam null: lam = 1.  eps = 0, lam = 1: t is the
+// one-hot row and every output carries xent_mean_kernel's bits.
+__global__ __launch_bounds__(256) void xent_mean_soft_kernel(
+    const float* __restrict__ logits, const int* __restrict__ labels,
+    const int* __restrict__ labels2, const float* __restrict__ lam_rows, float eps, int B, int C,
+    float* __restrict__ loss_rows, float* __restrict__ dlogits, float* __restrict__ mean_out,
+    int* __restrict__ correct) {
+  __shared__ float part[4];
+  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+  const float uni = eps / (float)C;
+  float acc = 0.f;
+  for (int row = w; row < B; row += 4) {
+    const int lab = labels[row];
+    const int lab2 = lam_rows ? labels2[row] : lab;
+    const float lam = lam_rows ? lam_rows[row] : 1.f;
+    const float* lg = logits + (size_t)row * C;
+    float mx = -INFINITY;
+    for (int c = lane; c < C; c += 64) mx = fmaxf(mx, lg[c]);
+    mx = wave_max(mx);
+    float se = 0.f;
+    for (int c = lane; c < C; c += 64) se += __expf(lg[c] - mx);
+    se = wave_sum(se);
+    int am = C;
+    for (int c = lane; c < C; c += 64)
+      if (lg[c] == mx) am = min(am, c);
+    for (int o = 32; o > 0; o >>= 1) am = min(am, __shfl_xor(am, o, 64));
+    float tz = 0.f;
+    for (int c = lane; c < C; c += 64) {
+      const float a = (c == lab ? lam : 0.f) + (c == lab2 ? 1.f - lam : 0.f);
+      const float t = (1.f - eps) * a + uni;
+      tz += t * lg[c];
+      dlogits[(size_t)row * C + c] = (__expf(lg[c] - mx) / se - t) / (float)B;
+    }
+    tz = wave_sum(tz);
+    const float l = logf(se) + mx - tz;
+    if (lane == 0) {
+      loss_rows[row] = l;
+      if (correct && am == lab) atomicAdd(correct, 1);
+    }
+    acc += l;
+  }
+  if (lane == 0) part[w] = acc;
+  __syncthreads();
+  if (threadIdx.x == 0) mean_out[0] = (part[0] + part[1] + part[2] + part[3]) / (float)B;
+}
+
 // Small fully connected layers (LeNet-5's 400-120-84-10 at batch 64, the
 // ResNet-18 512 -> 10 head at batch 32-128): far below MFMA tile sizes, so
 // plain VALU dot products with one output per thread; deterministic.
@@ -870,6 +919,20 @@ __global__ __launch_bounds__(256) void gather_batch_kernel(const float* __restri
   for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < n / 4; i += stride)
     dst[i] = src[i];
   if (blockIdx.x == 0 && threadIdx.x < batch) yb[threadIdx.x] = labels[off + threadIdx.x];
+}
+
+// ... and the partner labels and shares of the same rows (--mix)
+__global__ __launch_bounds__(256) void gather_soft_kernel(const int* __restrict__ labels2,
+                                                          const float* __restrict__ lam,
+                                                          const long long* step, int n_local,
+                                                          int batch, int* __restrict__ y2b,
+                                                          float* __restrict__ lamb) {
+  const long long s = step ? *step : 0;
+  const long long off = (s * batch) % (long long)(n_local - batch);
+  if (threadIdx.x < batch) {
+    y2b[threadIdx.x] = labels2[off + threadIdx.x];
+    lamb[threadIdx.x] = lam[off + threadIdx.x];
+  }
 }
 
 // dx = dy * [y > 0]
@@ -1403,6 +1466,23 @@ void relu_bwd(const float* dy, const float* y, float* dx, long long n, hipStream
 void lr_from_step(const long long* step, int n_local, int batch, float base, float decay,
                   float* lr, hipStream_t st) {
   lr_kernel<<<1, 1, 0, st>>>(step, n_local, batch, base, decay, lr);
+}
+
+void xent_mean_soft(const float* logits, const int* labels, const int* labels2, const float* lam,
+                    float eps, int B, int C, float* loss_rows, float* dlogits, float* mean,
+                    int* correct, hipStream_t st) {
+  if (lam && !labels2) throw std::runtime_error("xent_mean_soft: lam without labels2");
+  if (!(eps >= 0.f && eps < 1.f)) throw std::runtime_error("xent_mean_soft: eps not in [0, 1)");
+  xent_mean_soft_kernel<<<1, 256, 0, st>>>(logits, labels, labels2, lam, eps, B, C, loss_rows,
+                                           dlogits, mean, correct);
+}
+
+void gather_soft(const int* labels2, const float* lam, const long long* step, int n_local,
+                 int batch, int* y2b, float* lamb, hipStream_t st) {
+  if (batch > 256 || batch <= 0 || n_local <= batch)
+    throw std::runtime_error("gather_soft: unsupported shape");
+  if (!labels2 || !lam || !y2b || !lamb) throw std::runtime_error("gather_soft: null buffer");
+  gather_soft_kernel<<<1, 256, 0, st>>>(labels2, lam, step, n_local, batch, y2b, lamb);
 }
 
 void gather_batch(const float* data, const int* labels, const long long* step, int n_local,

@@ -41,6 +41,9 @@ lenet::ImageArgs LenetExecutor::image_args() const {
   a.base_lr = p_.base_lr;
   a.lr_decay = p_.lr_decay;
   a.correct = P<int>(p_.correct);
+  a.y2 = P<const int>(p_.train_y2);
+  a.lam = P<const float>(p_.train_lam);
+  a.eps = p_.label_smoothing;
   return a;
 }
 

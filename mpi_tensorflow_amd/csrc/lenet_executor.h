@@ -26,6 +26,9 @@
 
 struct LenetPtrs {
   uintptr_t train_x = 0, train_y = 0;
+  // soft targets (--mix, --label-smoothing; kernels/lenet.h ImageArgs y2 / lam / eps)
+  uintptr_t train_y2 = 0, train_lam = 0;
+  float label_smoothing = 0.f;
   int n_local = 0, batch = 64;
   uintptr_t params = 0, grads = 0, mom = 0;
   long long total = 0;

@@ -98,7 +98,8 @@ void MnistExecutor::enqueue_fwd_bwd(hipStream_t s, bool finalize,
                               P<float>(p.dh), P<float>(p.dlog), P<float>(p.loss_rows),
                               P<float>(p.lr), P<int>(p.correct), s, nullptr, nullptr,
                               fc1_t ? mnist::fc1_train_t_splits() : mnist::fc1_train_splits(),
-                              p.batch);
+                              p.batch, P<const int>(p.train_y2), P<const float>(p.train_lam),
+                              p.label_smoothing);
   if (factors && sched_ == SCHED_FACTORS) HIP_CHECK(hipEventRecord(ev_fac_, s));
   // backward: fc1 dX (+pool2/ReLU2 scatter) | dW1 | fc2 grads, one launch
   // (SCHED_XGMI_FAC: dX | the peers' factor rows over the links)
@@ -205,7 +206,9 @@ void MnistExecutor::enqueue_fwd_bwd_bf16(hipStream_t s, bool finalize,
                               p.keep_prob, p.seed, p.rank, p.base_lr, p.lr_decay, P<float>(p.hd),
                               P<float>(p.dh), P<float>(p.dlog), P<float>(p.loss_rows),
                               P<float>(p.lr), P<int>(p.correct), s, P<U16>(p.dh16),
-                              P<U16>(p.dht16), mnist::fc1_train_splits(), p.batch);
+                              P<U16>(p.dht16), mnist::fc1_train_splits(), p.batch,
+                              P<const int>(p.train_y2), P<const float>(p.train_lam),
+                              p.label_smoothing);
   mnist16::launch_fc1_bwd(P<const U16>(p.a2h), P<const U16>(p.a2t), P<const uint8_t>(p.idx2),
                           P<const U16>(p.dh16), P<const U16>(p.dht16), P<const float>(p.hd),
                           P<const float>(p.dh), P<const float>(p.dlog), P<const U16>(p.w1b), B,

@@ -43,6 +43,11 @@ struct MnistPtrs {
   // backward pass with exact zeros for the pad rows, so they add nothing to
   // any gradient.
   int batch_pad = 0;
+  // soft targets (--mix, --label-smoothing; kernels/mnist.h launch_fc_head_train):
+  // the partner label and the own label's share of every row of train_y (0:
+  // lam = 1), and the smoothing; all zero = the hard-label head
+  uintptr_t train_y2 = 0, train_lam = 0;
+  float label_smoothing = 0.f;
   // flat buffers
   uintptr_t params = 0, grads = 0, mom = 0;
   long long total = 0, l2_end = 0, bucket1 = 0;  // floats

@@ -1251,8 +1251,46 @@ class _XentFn(torch.autograd.Function):
         return dlog * g, None
 
 
-def cross_entropy(logits: torch.Tensor, labels: torch.Tensor) -> torch.Tensor:
-    """mean softmax cross-entropy; labels int32 on GPU."""
+class _XentSoftFn(torch.autograd.Function):
+    """`_XentFn` against a soft target (xent_mean_soft_kernel): labels2 / lam may
+    be None (lam = 1)."""
+
+    @staticmethod
+    def forward(ctx, logits, labels, labels2, lam, eps):
+        C = native()
+        logits = logits.contiguous()
+        B, K = logits.shape
+        loss_rows = torch.empty(B, device=logits.device)
+        dlog = torch.empty_like(logits)
+        mean = torch.empty((), device=logits.device)
+        C.ops.xent_mean_soft(ptr(logits), ptr(labels), ptr(labels2) if lam is not None else 0,
+                             ptr(lam) if lam is not None else 0, float(eps), B, K,
+                             ptr(loss_rows), ptr(dlog), ptr(mean), 0, stream_handle())
+        ctx.save_for_backward(dlog)
+        return mean
+
+    @staticmethod
+    def backward(ctx, g):
+        (dlog,) = ctx.saved_tensors
+        if _UNIT_SEED:
+            return dlog, None, None, None, None
+        return dlog * g, None, None, None, None
+
+
+def cross_entropy(logits: torch.Tensor, labels: torch.Tensor, labels2=None, lam=None,
+                  eps: float = 0.0) -> torch.Tensor:
+    """mean softmax cross-entropy; labels int32 on GPU.  With `lam` (and
+    `labels2`) or eps > 0 the target is soft (docs/ACCURACY.md): t = (1 - eps)
+    (lam onehot(labels) + (1 - lam) onehot(labels2)) + eps / classes."""
+    if (lam is None) != (labels2 is None):
+        raise ValueError("cross_entropy: labels2 and lam come together")
+    if lam is None and eps == 0.0:  # nothing soft was asked for: the hard-label route
+        if logits.is_cuda and not _ORACLE:
+            return _XentFn.apply(logits, labels.to(torch.int32))
+        return F.cross_entropy(logits, labels.long())
     if logits.is_cuda and not _ORACLE:
-        return _XentFn.apply(logits, labels.to(torch.int32))
-    return F.cross_entropy(logits, labels.long())
+        l2 = labels2.to(torch.int32).contiguous() if lam is not None else None
+        lm = lam.to(torch.float32).contiguous() if lam is not None else None
+        return _XentSoftFn.apply(logits, labels.to(torch.int32), l2, lm, float(eps))
+    from ..utils.rng import soft_xent_torch
+    return soft_xent_torch(logits, labels, labels2, lam, eps)

@@ -49,7 +49,10 @@ class EngineBase:
         self.drop_rank = 0 if cfg.same_seed_all_ranks else rank
         # force_sync: exercise the collective path at world 1
         self.grad_sync = comm is not None and (force_sync or (cfg.sync == "grad" and world > 1))
-        self.shuffler = None  # cfg.shuffle / cfg.augment: the per-pass rows (runtime/shuffle.py)
+        # cfg.shuffle / cfg.augment / cfg.mix: the per-pass rows (runtime/shuffle.py)
+        self.shuffler = None
+        # cfg.label_smoothing: the EPS of the soft training target (0: the hard label)
+        self.label_smoothing = float(getattr(cfg, "label_smoothing", 0.0) or 0.0)
         # cfg.ema: the moving average of `params` (same layout; init_ema), else None
         self.ema: Optional[torch.Tensor] = None
         self.ema_decay, self.ema_every = C.parse_ema(cfg.ema) if cfg.ema is not None else (0.0, 1)
@@ -70,6 +73,26 @@ class EngineBase:
         counter, which the SGD has incremented; no host read)."""
         Fn.ema_update(self.ema, self.params, self.step_dev if step is None else step,
                       self.ema_decay, self.ema_every)
+
+    @property
+    def soft_targets(self) -> bool:
+        """The training loss takes a soft target (--label-smoothing, --mix)."""
+        return self.label_smoothing > 0.0 or self.mix_rows() is not None
+
+    def mix_rows(self):
+        """(work_y2, work_lam) of the shuffler under cfg.mix, else None."""
+        sh = self.shuffler
+        return (sh.work_y2, sh.work_lam) if sh is not None and sh.mix is not None else None
+
+    def soft_loss_torch(self, logits: torch.Tensor, y: torch.Tensor, off: int) -> torch.Tensor:
+        """The PyTorch paths' mean loss of the batch at row `off` of the working
+        copy: the soft-target formula under the flags, else the hard-label one."""
+        if not self.soft_targets:
+            return torch.nn.functional.cross_entropy(logits, y.long())
+        from ..utils.rng import soft_xent_torch
+        m = self.mix_rows()
+        y2, lam = (t[off:off + y.shape[0]] for t in m) if m is not None else (None, None)
+        return soft_xent_torch(logits, y, y2, lam, self.label_smoothing)
 
     def param_views(self) -> Dict[str, torch.Tensor]:
         return self.layout.views(self.params)

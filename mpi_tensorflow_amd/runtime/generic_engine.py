@@ -133,6 +133,11 @@ class GenericEngine(EngineBase):
                                       image_shape=tuple(self.train_x.shape[1:]))
         if self.shuffler is not None:
             self.train_x, self.train_y = self.shuffler.work_x, self.shuffler.work_y
+        # cfg.mix: the partner labels and shares of the step's rows, gathered beside yb
+        self.y2b = self.lamb = None
+        if self.on_gpu and self.mix_rows() is not None:
+            self.y2b = torch.zeros(self.B, dtype=torch.int32).to(device)
+            self.lamb = torch.ones(self.B).to(device)
 
     # ------------------------------------------------------------------ util
     @property
@@ -256,8 +261,15 @@ class GenericEngine(EngineBase):
                             self.B, row, ptr(self.xb), ptr(self.yb), s, self.cfg.base_lr,
                             self.cfg.lr_decay, ptr(self.lr_dev))
         self._lr_fresh = True
+        if self.y2b is not None:
+            y2, lam = self.mix_rows()
+            C_.ops.gather_soft(ptr(y2), ptr(lam), ptr(self.step_dev), self.n_local, self.B,
+                               ptr(self.y2b), ptr(self.lamb), s)
         logits = self.model.forward(self.P, self.bn, self.xb, True)
-        loss = Fn.cross_entropy(logits, self.yb)
+        if self.soft_targets:
+            loss = Fn.cross_entropy(logits, self.yb, self.y2b, self.lamb, self.label_smoothing)
+        else:
+            loss = Fn.cross_entropy(logits, self.yb)
         # keep the device scalar itself (no copy launch): under graph capture its
         # storage is the graph's, rewritten by every replay
         self._loss_t = loss.detach()
@@ -306,7 +318,12 @@ class GenericEngine(EngineBase):
         y = self.train_y[off:off + self.B]
         self.params.grad = None
         logits = self.model.forward(self.P, self.bn, x, True)
-        loss = Fn.cross_entropy(logits, y)
+        if self.soft_targets:
+            m = self.mix_rows()
+            y2, lam = (t[off:off + self.B] for t in m) if m is not None else (None, None)
+            loss = Fn.cross_entropy(logits, y, y2, lam, self.label_smoothing)
+        else:
+            loss = Fn.cross_entropy(logits, y)
         loss.backward()
         with torch.no_grad():
             self.grads.copy_(self.params.grad)

@@ -87,6 +87,9 @@ class NativeLenetEngine(GraphStepDriver, EngineBase):
         p = C_.LenetPtrs()
         p.train_x, p.train_y = ptr(self.train_x), ptr(self.train_y)
         p.n_local, p.batch = self.n_local, self.B
+        if self.mix_rows() is not None:  # cfg.mix / cfg.label_smoothing: the soft xent wave
+            p.train_y2, p.train_lam = (ptr(t) for t in self.mix_rows())
+        p.label_smoothing = self.label_smoothing
         p.params, p.grads, p.mom = ptr(self.params), ptr(self.grads), ptr(self.mom)
         p.total = self.layout.total
         off = C_.LenetOffsets()

@@ -101,7 +101,7 @@ class TorchMnistEngine(MnistEngineBase):
         y = self.train_y[off:off + self.B]
         views = {k: v.detach().clone().requires_grad_(True) for k, v in self.param_views().items()}
         logits = M.forward(views, x, self.dropout_mask(step, self.B), self.cfg.dropout_keep)
-        data_loss = torch.nn.functional.cross_entropy(logits, y)
+        data_loss = self.soft_loss_torch(logits, y, off)
         grads = torch.autograd.grad(data_loss, [views[s.name] for s in self.layout.specs])
         gv = self.layout.views(self.grads)
         for s, g in zip(self.layout.specs, grads):
@@ -272,6 +272,11 @@ class NativeMnistEngine(GraphStepDriver, MnistEngineBase):
         p = C_.MnistPtrs()
         p.train_x, p.train_y = ptr(self.train_x), ptr(self.train_y)
         p.n_local, p.batch, p.batch_pad = self.n_local, self.B, self.Bp
+        # cfg.mix / cfg.label_smoothing: the head reads the partner labels and the
+        # shares beside the working copy's labels (pad rows included) and EPS
+        if self.mix_rows() is not None:
+            p.train_y2, p.train_lam = (ptr(t) for t in self.mix_rows())
+        p.label_smoothing = self.label_smoothing
         p.params, p.grads, p.mom = ptr(self.params), ptr(self.grads), ptr(self.mom)
         lay = self.layout
         p.total = lay.total

@@ -26,6 +26,15 @@ draw chain continued (`rng.affine_params`), a per-row inverse affine map with
 bilinear sampling (`rng.affine_np` is the definition), still one launch
 (`affine_rows`), reading one 3 x 129 int32 table uploaded at construction.
 Specs without those items keep the shift / flip load unchanged.
+
+With mix on (--mix mixup:M / cutmix:M) the pass as loaded above is blended row
+by row with partner rows of the same pass (`rng.mix_params` / `rng.mix_np` are
+the definition; the draw of a row is a pure function of (seed, rank, pass,
+working row index)).  The loader then writes a staging copy (`mid_x` /
+`mid_y`; with neither shuffle nor augment the pristine copy itself serves) and
+one `mix_rows` launch writes the working copy together with `work_y2` (the
+partner's label) and `work_lam` (the row's own share), which the soft-target
+loss reads beside `work_y`.
 """
 
 from __future__ import annotations
@@ -60,7 +69,8 @@ class PassShuffler:
     (augment only)."""
 
     def __init__(self, seed: int, rank: int, n_local: int, batch: int, work_x: torch.Tensor,
-                 work_y: torch.Tensor, native=None, augment=None, shuffle: bool = True):
+                 work_y: torch.Tensor, native=None, augment=None, shuffle: bool = True,
+                 mix=None):
         self.seed, self.rank, self.n, self.B = int(seed), int(rank), int(n_local), int(batch)
         self.shuffle = bool(shuffle)
         self.augment = None
@@ -97,6 +107,27 @@ class PassShuffler:
         self._C = native
         if native is not None and (work_x.dtype != torch.float32 or work_y.dtype != torch.int32):
             raise TypeError("shuffle_rows moves fp32 rows and int32 labels")
+        # mix = (kind, M): every loaded pass blended with partner rows; work_y2 /
+        # work_lam have the rows of work_y (pad rows: label 0, share 1)
+        self.mix = None
+        self.mix_table = None
+        self.work_y2 = self.work_lam = None
+        self.mid_x, self.mid_y = self.src_x, self.src_y
+        if mix is not None:
+            kind, M = mix
+            if work_x.dim() != 4:
+                raise ValueError(f"mix: rows of shape {tuple(work_x.shape[1:])} are not images")
+            H, W, C = (int(v) for v in work_x.shape[1:])
+            self.mix = (str(kind), float(M), (H, W, C))
+            self.mix_table = rng.mix_table(kind, M, H, W)
+            self.work_y2 = torch.zeros_like(self.work_y)
+            self.work_lam = torch.ones(self.work_y.shape[0], dtype=torch.float32,
+                                       device=self.work_y.device)
+            if native is not None:
+                self.mix_table = torch.from_numpy(self.mix_table).to(work_x.device)
+                if self.shuffle or self.augment is not None or self.affine is not None:
+                    self.mid_x = torch.empty_like(self.src_x)
+                    self.mid_y = torch.empty_like(self.src_y)
         self.loaded: Optional[int] = None  # the pass the working copy holds
 
     def key(self, p: int) -> int:
@@ -109,6 +140,15 @@ class PassShuffler:
     def augment_key(self, p: int) -> int:
         return rng.augment_key(self.seed, self.rank, p)
 
+    def mix_key(self, p: int) -> int:
+        return rng.mix_key(self.seed, self.rank, p)
+
+    def mix_params(self, p: int):
+        """The mix draws of pass p (rng.mix_params)."""
+        _, _, (H, W, _) = self.mix
+        table = self.mix_table.cpu().numpy() if torch.is_tensor(self.mix_table) else self.mix_table
+        return rng.mix_params(self.mix_key(p), self.n, table, H, W)
+
     def load(self, p: int) -> None:
         """Working copy := pristine rows in the order, and with the draws, of
         pass p, on the current stream (idempotent)."""
@@ -116,23 +156,34 @@ class PassShuffler:
             return
         if self._C is not None:
             from ..ops import ptr, stream_handle
-            if self.affine is not None:
+            # with mix the loader fills the staging copy and mix_rows the working one
+            out_x, out_y = ((self.work_x, self.work_y) if self.mix is None
+                            else (self.mid_x, self.mid_y))
+            if self.mix is not None and self.mid_x is self.src_x:  # mix alone: no staging load
+                pass
+            elif self.affine is not None:
                 spec, (H, W, C) = self.affine
-                self._C.ops.affine_rows(ptr(self.src_x), ptr(self.src_y), ptr(self.work_x),
-                                        ptr(self.work_y), self.n, H, W, C, self.shuffle,
+                self._C.ops.affine_rows(ptr(self.src_x), ptr(self.src_y), ptr(out_x),
+                                        ptr(out_y), self.n, H, W, C, self.shuffle,
                                         self.key(p) if self.shuffle else 0, self.augment_key(p),
                                         spec.K, spec.flip, spec.fill, ptr(self.tables),
                                         spec.cutout, stream_handle())
             elif self.augment is None:
-                self._C.ops.shuffle_rows(ptr(self.src_x), ptr(self.src_y), ptr(self.work_x),
-                                         ptr(self.work_y), self.n, self.row_elems, self.key(p),
+                self._C.ops.shuffle_rows(ptr(self.src_x), ptr(self.src_y), ptr(out_x),
+                                         ptr(out_y), self.n, self.row_elems, self.key(p),
                                          stream_handle())
             else:
                 K, flip, fill, (H, W, C) = self.augment
-                self._C.ops.augment_rows(ptr(self.src_x), ptr(self.src_y), ptr(self.work_x),
-                                         ptr(self.work_y), self.n, H, W, C, self.shuffle,
+                self._C.ops.augment_rows(ptr(self.src_x), ptr(self.src_y), ptr(out_x),
+                                         ptr(out_y), self.n, H, W, C, self.shuffle,
                                          self.key(p) if self.shuffle else 0, self.augment_key(p),
                                          K, flip, fill, stream_handle())
+            if self.mix is not None:
+                kind, _, (H, W, C) = self.mix
+                self._C.ops.mix_rows(ptr(self.mid_x), ptr(self.mid_y), ptr(self.work_x),
+                                     ptr(self.work_y), ptr(self.work_y2), ptr(self.work_lam),
+                                     self.n, H, W, C, kind == "cutmix", self.mix_key(p),
+                                     ptr(self.mix_table), stream_handle())
         else:
             rows = self.perm(p)
             x, y = self.src_x, self.src_y
@@ -147,6 +198,10 @@ class PassShuffler:
                 K, flip, fill, _ = self.augment
                 x = rng.augment_torch(x, *rng.augment_params(self.augment_key(p), rows, K, flip),
                                       fill)
+            if self.mix is not None:
+                x, y, y2, lam = rng.mix_torch(x, y, self.mix_params(p), self.mix[0])
+                self.work_y2[:self.n] = y2
+                self.work_lam[:self.n] = lam
             self.work_x[:self.n] = x
             self.work_y[:self.n] = y
         self.loaded = p
@@ -169,13 +224,17 @@ class PassShuffler:
 
 def make_shuffler(cfg, rank: int, n_local: int, work_x: torch.Tensor, work_y: torch.Tensor,
                   native=None, image_shape=None) -> Optional[PassShuffler]:
-    """The engine's shuffler, or None (nothing allocated) with shuffle and
-    augment off.  `rank` is the rank of the engine's dropout stream (0 under
+    """The engine's shuffler, or None (nothing allocated) with shuffle,
+    augment and mix off.  `rank` is the rank of the engine's dropout stream (0 under
     quirk Q14); `image_shape`: (H, W, C) of a row, which augment needs."""
     shuffle = bool(getattr(cfg, "shuffle", False))
     spec = getattr(cfg, "augment", None)
-    if not shuffle and spec is None:
+    mix = getattr(cfg, "mix", None)
+    if not shuffle and spec is None and mix is None:
         return None
+    if mix is not None:
+        from ..config import parse_mix
+        mix = parse_mix(mix)
     augment = None
     if spec is not None:
         from ..config import parse_augment_spec
@@ -184,4 +243,4 @@ def make_shuffler(cfg, rank: int, n_local: int, work_x: torch.Tensor, work_y: to
         s, shape = parse_augment_spec(spec, cfg.model), tuple(int(v) for v in image_shape)
         augment = (s, shape) if s.affine else (s.K, s.flip, s.fill, shape)
     return PassShuffler(cfg.seed, rank, n_local, cfg.batch_size, work_x, work_y, native,
-                        augment=augment, shuffle=shuffle)
+                        augment=augment, shuffle=shuffle, mix=mix)

@@ -76,8 +76,13 @@ class RunSummary:
     final_ema_test_error_local: Optional[float] = None
     final_ema_test_error_global: Optional[float] = None
 
+    # --label-smoothing / --mix only: the run's soft-target flags as given
+    label_smoothing: Optional[float] = None
+    mix: Optional[str] = None
+
     _OPTIONAL = ("final_test_loss", "final_val_error", "final_val_loss",
-                 "final_ema_test_error_local", "final_ema_test_error_global")
+                 "final_ema_test_error_local", "final_ema_test_error_global",
+                 "label_smoothing", "mix")
 
     def as_dict(self) -> Dict:
         d = dataclasses.asdict(self)
@@ -364,15 +369,35 @@ class Trainer:
         else:
             off = batch_offset(step, n, B)
             rows = np.arange(off, off + B)
-        x = sh.train_x[rows]
-        if cfg.augment is not None:  # ... with this pass's draws for each of them
-            spec = C.parse_augment_spec(cfg.augment, cfg.model)
-            key = rng.augment_key(cfg.seed, rank, pass_of(step, n, B))
-            if spec.affine:
-                q = rng.affine_params(key, rows, spec, *x.shape[1:3])
-                x = rng.affine_np(x, q.m, q.dy, q.dx, q.flipped, spec.fill, q.cutout)
-            else:
-                x = rng.augment_np(x, *rng.augment_params(key, rows, spec.K, spec.flip), spec.fill)
+        p = pass_of(step, n, B)
+
+        def loaded(rows):  # the shard rows `rows` as the pass's loader shows them
+            x = sh.train_x[rows]
+            if cfg.augment is not None:  # ... with this pass's draws for each of them
+                spec = C.parse_augment_spec(cfg.augment, cfg.model)
+                key = rng.augment_key(cfg.seed, rank, p)
+                if spec.affine:
+                    q = rng.affine_params(key, rows, spec, *x.shape[1:3])
+                    return rng.affine_np(x, q.m, q.dy, q.dx, q.flipped, spec.fill, q.cutout)
+                return rng.augment_np(x, *rng.augment_params(key, rows, spec.K, spec.flip),
+                                      spec.fill)
+            return x
+
+        x = loaded(rows)
+        if cfg.mix is not None:  # ... blended with their partner rows of the pass
+            kind, M = C.parse_mix(cfg.mix)
+            H, W = x.shape[1:3]
+            order = (rng.shuffle_perm(rng.shuffle_key(cfg.seed, rank, p), n) if cfg.shuffle
+                     else np.arange(n))
+            off = batch_offset(step, n, B)
+            q = [v[off:off + B] for v in rng.mix_params(rng.mix_key(cfg.seed, rank, p), n,
+                                                        rng.mix_table(kind, M, H, W), H, W)]
+            # the batch's rows, then their partners (which mix with nothing)
+            both = np.concatenate([x, loaded(order[q[0]])])
+            ident = [np.arange(B, 2 * B), np.full(B, 65536)] + [np.zeros(B, np.int64)] * 4
+            q[0] = np.arange(B, 2 * B)
+            prm = [np.concatenate([a, b]) for a, b in zip(q, ident)]
+            x = rng.mix_np(both, np.zeros(2 * B, np.int64), prm, kind)[0][:B]
         return self.eval_prediction(x, dropout=True)
 
     def check_replicas(self, step: int, averaged: bool = False) -> None:
@@ -515,7 +540,8 @@ class Trainer:
             sync_schedule=self.sync_schedule(), xgmi_gate=self.comms.xgmi_status,
             final_test_loss=extra.get("test_loss"), final_val_error=extra.get("val_error"),
             final_val_loss=extra.get("val_loss"),
-            final_ema_test_error_local=ema_err, final_ema_test_error_global=ema_err_g)
+            final_ema_test_error_local=ema_err, final_ema_test_error_global=ema_err_g,
+            label_smoothing=cfg.label_smoothing if cfg.label_smoothing > 0 else None, mix=cfg.mix)
         self.metrics.write(final=True, **summary.as_dict(), **extra)
         if cfg.ckpt:
             self.save_checkpoint(cfg.ckpt)

@@ -29,6 +29,7 @@ STEP_MUL = 0x85EBCA6B
 EVAL_SALT = 0x5BD1E995  # separates the eval-time (quirk Q8) stream
 SHUFFLE_SALT = 0x2545F491  # ... and the per-pass row order (--shuffle)
 AUGMENT_SALT = 0x68E31DA4  # ... and the per-pass shift / flip draws (--augment)
+MIX_SALT = 0x3C6EF372  # ... and the per-pass mixup / cutmix draws (--mix)
 
 
 def _mix_np(x: np.ndarray) -> np.ndarray:
@@ -317,6 +318,136 @@ def affine_torch(x_nhwc, m, dy, dx, flipped, fill: float, cutout=None):
             o = torch.where(hole[..., None], fv, o)
         out[z] = o
     return out
+
+
+# ---- mixup / cutmix and soft targets (--mix, --label-smoothing) -------------
+# Integer draws and a Q16 table, single fp32 operations per pixel, so numpy,
+# torch and augment::mix_rows (csrc/kernels/augment.hip) agree bit for bit; docs/ACCURACY.md spells the
+# definition out.
+MIX_LEVELS = 129  # level 0 is "no mixing"
+
+
+def mix_key(seed: int, rank: int, pass_: int) -> int:
+    """Key of the mix draws of training pass `pass_` (--mix); `rank` as in
+    `shuffle_key`."""
+    return dropout_key(seed, rank, pass_, MIX_SALT)
+
+
+def mix_table(kind: str, M: float, H: int, W: int) -> np.ndarray:
+    """int32 [3, 129]: wq | bh | bw of the levels l = 0..128, Mq = rint(65536 M / 100).
+    mixup: wq[l] = (Mq l + 64) >> 7 (the partner's share in Q16), no box.
+    cutmix: a = (Mq l + 64) >> 7, bh = min(H, floor(H sqrt(a / 65536) + 0.5)), bw
+    likewise with W, wq = rint(65536 bh bw / (H W)): the share the box really has.
+    Computed in float64; the oracle and the kernel read this one table."""
+    if kind not in ("mixup", "cutmix"):
+        raise ValueError(f"unknown mix kind {kind!r}")
+    Mq = int(np.rint(65536.0 * float(M) / 100.0))
+    a = (Mq * np.arange(MIX_LEVELS, dtype=np.int64) + 64) >> 7
+    if kind == "mixup":
+        z = np.zeros(MIX_LEVELS, np.int64)
+        return np.stack([a, z, z]).astype(np.int32)
+    r = np.sqrt(a.astype(np.float64) / 65536.0)
+    bh = np.minimum(H, np.floor(H * r + 0.5)).astype(np.int64)
+    bw = np.minimum(W, np.floor(W * r + 0.5)).astype(np.int64)
+    wq = np.rint(65536.0 * (bh * bw).astype(np.float64) / float(H * W)).astype(np.int64)
+    return np.stack([wq, bh, bw]).astype(np.int32)
+
+
+def mix_params(key: int, n: int, table, H: int, W: int):
+    """(partner, lamq, cy, cx, bh, bw) of the working rows i = 0..n-1 of a pass
+    under `key`, int64 each; lam = lamq 2^-16 is the row's own share.
+
+        g0 = mix(key ^ i), g1 = mix(g0 + GOLDEN), g2 = mix(g1 + GOLDEN)
+        level = g0 % 129, lamq = 65536 - wq[level], bh, bw = table[1:, level]
+        partner = shuffle_perm(mix(key ^ GOLDEN), n)[i]
+        cy = g1 % (H - bh + 1), cx = g2 % (W - bw + 1)
+    """
+    T = np.asarray(table).astype(np.int64).reshape(3, MIX_LEVELS)
+    i = np.arange(n, dtype=np.uint64)
+    g0 = _mix_np(i ^ np.uint64(key))
+    g1 = _mix_np(g0 + np.uint64(GOLDEN))
+    g2 = _mix_np(g1 + np.uint64(GOLDEN))
+    level = (g0 % np.uint64(MIX_LEVELS)).astype(np.int64)
+    bh, bw = T[1][level], T[2][level]
+    pkey = int(_mix_np(np.array([(key ^ GOLDEN) & M32], np.uint64))[0])
+    partner = shuffle_perm(pkey, n)
+    cy = (g1 % (H - bh + 1).astype(np.uint64)).astype(np.int64)
+    cx = (g2 % (W - bw + 1).astype(np.uint64)).astype(np.int64)
+    return partner, 65536 - T[0][level], cy, cx, bh, bw
+
+
+def _mix_box(xp, H, W, cy, cx, bh, bw, **kw):
+    ys, xs = xp.arange(H, **kw)[None, :, None], xp.arange(W, **kw)[None, None, :]
+    cy, cx, bh, bw = (v[:, None, None] for v in (cy, cx, bh, bw))
+    return ((ys >= cy) & (ys < cy + bh) & (xs >= cx) & (xs < cx + bw))[..., None]
+
+
+def mix_np(A: np.ndarray, A_y: np.ndarray, params, kind: str):
+    """The mixed pass (x, y1, y2, lam) of the NHWC fp32 pass A with labels A_y.
+    mixup: x[i] = lam A[i] + w A[j], w = 1 - lam, each product and the sum one
+    rounded fp32 operation; cutmix: x[i] = A[j] inside the row's box, A[i]
+    elsewhere.  y1 = A_y, y2 = A_y[j], lam float32 (exact: a multiple of 2^-16)."""
+    A = np.asarray(A)
+    j, lamq, cy, cx, bh, bw = (np.asarray(v, np.int64) for v in params)
+    lam = lamq.astype(np.float32) * np.float32(2.0 ** -16)
+    if kind == "mixup":
+        w = (65536 - lamq).astype(np.float32) * np.float32(2.0 ** -16)
+        sh = (-1,) + (1,) * (A.ndim - 1)
+        x = lam.reshape(sh) * A + w.reshape(sh) * A[j]
+    else:
+        _, H, W, _ = A.shape
+        x = np.where(_mix_box(np, H, W, cy, cx, bh, bw), A[j], A)
+    y = np.asarray(A_y)
+    return x.astype(A.dtype), y.copy(), y[j], lam
+
+
+def mix_torch(A, A_y, params, kind: str):
+    """`mix_np` on torch tensors, on their device (the parameters: numpy)."""
+    import torch
+
+    dev = A.device
+
+    def dev64(v):
+        return torch.from_numpy(np.ascontiguousarray(np.asarray(v, np.int64))).to(dev)
+
+    j, lamq, cy, cx, bh, bw = (dev64(v) for v in params)
+    lam = lamq.to(torch.float32) * 2.0 ** -16
+    if kind == "mixup":
+        w = (65536 - lamq).to(torch.float32) * 2.0 ** -16
+        sh = (-1,) + (1,) * (A.dim() - 1)
+        x = lam.reshape(sh) * A + w.reshape(sh) * A[j]
+    else:
+        _, H, W, _ = A.shape
+        x = torch.where(_mix_box(torch, H, W, cy, cx, bh, bw, device=dev), A[j], A)
+    return x, A_y.clone(), A_y[j], lam
+
+
+def soft_targets(y1, y2, lam, eps: float, classes: int) -> np.ndarray:
+    """float64 [n, classes]: t = (1 - eps) (lam onehot(y1) + (1 - lam) onehot(y2))
+    + eps / classes; y2 / lam None: lam = 1."""
+    y1 = np.asarray(y1).astype(np.int64)
+    n = y1.shape[0]
+    lam = np.ones(n) if lam is None else np.asarray(lam, np.float64)
+    y2 = y1 if y2 is None else np.asarray(y2).astype(np.int64)
+    a = np.zeros((n, classes), np.float64)
+    a[np.arange(n), y1] += lam
+    a[np.arange(n), y2] += 1.0 - lam
+    return (1.0 - float(eps)) * a + float(eps) / classes
+
+
+def soft_xent_torch(logits, y1, y2=None, lam=None, eps: float = 0.0):
+    """Mean soft-target cross-entropy of the torch paths, -(t log_softmax(z)).sum(1).mean(),
+    with t formed in float64 as `soft_targets` forms it and rounded once to the
+    dtype of the logits."""
+    import torch
+
+    C = logits.shape[1]
+    a = torch.nn.functional.one_hot(y1.long(), C).double()
+    if lam is not None:
+        l = lam.double()[:, None]
+        a = l * a + (1.0 - l) * torch.nn.functional.one_hot(y2.long(), C).double()
+    t = ((1.0 - float(eps)) * a + float(eps) / C).to(logits.dtype)
+    return -(t * torch.log_softmax(logits, 1)).sum(1).mean()
 
 
 def keep_mask_np(key: int, n: int, keep_prob: float) -> np.ndarray:

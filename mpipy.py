@@ -10,7 +10,8 @@ module global, /root/reference/mpipy.py:14-21).  Here:
 with optional overrides (see --help): --epochs, --batch-size, --model
 {mnist_cnn,lenet5,resnet18}, --sync {grad,param_avg,none}, --sync-every,
 --eval-every, --synthetic, --ckpt/--resume, --metrics-jsonl,
---eval-metrics, --ckpt-best, --ema, --reference-quirks.  Log lines keep the reference's exact formats.
+--eval-metrics, --ckpt-best, --ema, --label-smoothing, --mix, --reference-quirks.
+Log lines keep the reference's exact formats.
 
     python mpipy.py --resume best.npz --predict test           # evaluate a checkpoint
     python mpipy.py --resume best.npz --predict digits.npy --predict-out p.npz
