@@ -302,7 +302,7 @@ struct Loader {
     }
 #pragma unroll
     for (int i = 0; i < BR; ++i) {
-      const int n = min(n0 + (tid >> 3) + (NT / 8) * i, s.K - 1);  // K % 64 == 0: never clamps
+      const int n = min(n0 + (tid >> 3) + (NT / 8) * i, s.K - 1);  // K % BN == 0 (plan): never clamps
       bbase[i] = wt + (size_t)n * s.C + 8 * c8;
     }
   }
@@ -1763,7 +1763,9 @@ static inline Plan plan(const ConvShape& s, bool epilogue) {
   const Tile order[4] = {T128x128, T128x64, T64x128, T64x64};
   Tile t = T64x64;
   for (Tile c : order) {
-    if (tn(c) > s.K) continue;
+    // whole column tiles only (as wg_plan): the epilogues store, and read
+    // bias / shift / addend, without a column guard
+    if (s.K % tn(c) != 0) continue;
     if ((long long)cdiv(M, tm(c)) * cdiv(s.K, tn(c)) >= 256) {
       t = c;
       break;
@@ -2643,6 +2645,72 @@ void conv_bwd_filter_s2d_stem_bf16(const ConvShape& si, const void* xs, const vo
     wgrad_kernel<64, 64, true><<<blocks, NT, 0, st>>>(si, xh, dh, out, p.kchunk, si);
   }
   if (p.z > 1) slab_reduce(ws, p.z, 256LL * si.K / 4, dw8, st);
+}
+
+// The kernel, tile and split the launchers of this file take for s (follows
+// conv_fwd_bf16 / conv_bwd_data_bf16 / conv_bwd_filter_bf16 with the bf16
+// operand copies present, and the stem launchers), from their own plans.
+ConvRoute conv_route_bf16(const ConvShape& s, int op, bool epilogue, int stem) {
+  using namespace cbf;
+  ConvRoute r;
+  r.family = "bf16";
+  auto gemm = [&](const ConvShape& c, bool epi, const char* name) {
+    const Plan p = plan(c, epi);
+    r.kernel = name, r.bm = tm(p.t), r.bn = tn(p.t), r.z = p.z;
+  };
+  auto halo3 = [&](const ConvShape& c) {
+    const P3 p = plan3(c);
+    r.kernel = "conv3_kernel", r.bm = p.bm, r.bn = 64, r.z = p.z, r.halo = true;
+  };
+  auto wg = [&](const ConvShape& c) {
+    const WgPlan p = wg_plan(c);
+    r.kernel = "wgrad_kernel", r.bm = p.bm, r.bn = p.bn, r.z = p.z;
+  };
+  if (stem) {
+    r.stem = true;
+    if (op == 0) {
+      if (stem == 2) s2d_check(s);
+      r.kernel = stem == 2 ? (g_s2d_preload ? "fwd_kernel/S2dLoaderPre" : "fwd_kernel/S2dLoader")
+                           : "fwd_kernel/StemLoader";
+      r.bm = 128, r.bn = 64;
+    } else if (op == 2) {
+      wg(s);
+      if (stem == 1) r.kernel = "wgrad_kernel/StemWgLoader";
+    } else {
+      throw std::runtime_error("conv_route: the stem has no backward-data");
+    }
+    return r;
+  }
+  if (op == 0) {
+    if (!conv_fwd_bf16_ok(s)) throw std::runtime_error("conv_route: not a bf16-family forward");
+    if (!epilogue && conv3_ok(s))
+      halo3(s);
+    else
+      gemm(s, epilogue, "fwd_kernel");
+  } else if (op == 1) {
+    if (!conv_bwd_data_bf16_ok(s)) throw std::runtime_error("conv_route: not a bf16-family dgrad");
+    if (dgrad3s2_ok(s)) {
+      r.kernel = "dgrad3s2_kernel", r.bm = 64, r.bn = 64, r.z = plan3s2(s).z, r.halo = true;
+    } else if (dgrad_1x1s2(s)) {
+      ConvShape d = dgrad_shape(s);
+      d.H = d.OH = s.OH;
+      d.W = d.OW = s.OW;
+      gemm(d, true, "fwd_kernel/ex2");
+    } else if (conv3_ok(dgrad_shape(s))) {
+      halo3(dgrad_shape(s));
+    } else {
+      gemm(dgrad_shape(s), false, "fwd_kernel");
+    }
+  } else {
+    if (!conv_bwd_filter_bf16_ok(s)) throw std::runtime_error("conv_route: not a bf16-family wgrad");
+    if (wgrad3_ok(s)) {
+      r.kernel = "wgrad3_kernel", r.bm = w3::chunk_pixels(s), r.bn = 64, r.z = wgrad3_splits(s);
+      r.halo = true;
+    } else {
+      wg(s);
+    }
+  }
+  return r;
 }
 
 size_t s2d_stem_ws_floats(const ConvShape& si) {

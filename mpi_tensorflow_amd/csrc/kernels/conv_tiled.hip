@@ -1813,4 +1813,56 @@ void conv_bwd_filter_tiled(const ConvShape& s, const float* x, const float* dy, 
   if (z > 1) slab_sum(part, z, (long long)taps * s.C * s.K, dw, st);
 }
 
+// The kernel, tile and split this family's launchers take for s (follows
+// conv3f / conv_fwd_tiled / conv_bwd_data_tiled / conv_bwd_filter_tiled), from
+// their own plans.  The caller has checked the *_tiled_ok predicate.
+ConvRoute conv_route_tiled(const ConvShape& s, int op, bool bf16, bool epilogue, bool wcopy) {
+  using namespace tiled;
+  ConvRoute r;
+  r.family = "tiled";
+  auto halo = [&](const ConvShape& c) {
+    C3fPlan p;
+    conv3f_plan(c, p);
+    r.kernel = "conv3f_kernel", r.bm = p.bm, r.bn = p.bn, r.z = p.z, r.halo = true;
+  };
+  auto fwd = [&](const ConvShape& c, bool epi, bool b16) {
+    Tile t;
+    int z, kps;
+    fwd_plan(c, epi, b16, t, z, kps);
+    r.kernel = c.C % BK != 0 ? "fwd_kernel/gather" : "fwd_kernel";
+    r.bm = tile_m(t), r.bn = tile_n(t), r.z = z;
+  };
+  if (op == 0) {
+    if (!bf16 && wcopy && !epilogue && conv3f_ok(s))
+      halo(s);
+    else
+      fwd(s, epilogue, bf16);
+  } else if (op == 1) {
+    D3s2fPlan dp;
+    if (!bf16 && dgrad_fwd_ok(s)) {
+      if (conv3f_ok(dgrad_fwd_shape(s)))
+        halo(dgrad_fwd_shape(s));
+      else
+        fwd(dgrad_fwd_shape(s), false, false);
+    } else if (!bf16 && dgrad3s2f_plan(s, dp)) {
+      r.kernel = "dgrad3s2f_kernel", r.bm = 64, r.bn = 64, r.z = dp.z, r.halo = true;
+    } else {
+      Tile t;
+      int z, kps;
+      data_plan(s, bf16, t, z, kps);
+      r.kernel = "data_kernel", r.bm = tile_m(t), r.bn = tile_n(t), r.z = z;
+    }
+  } else {
+    int kchunk;
+    r.z = filter_splits(s, kchunk);
+    if (s.C % 4 != 0) {
+      r.kernel = "filter_gather_kernel", r.bm = 64, r.bn = 64;
+    } else {
+      const Tile t = filter_tile(s);
+      r.kernel = "filter_kernel", r.bm = tile_m(t), r.bn = tile_n(t);
+    }
+  }
+  return r;
+}
+
 }  // namespace gops

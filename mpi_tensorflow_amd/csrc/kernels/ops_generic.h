@@ -68,6 +68,25 @@ void conv_bwd_filter(const ConvShape& s, const float* x, const float* dy, float*
                      hipStream_t st, bool bf16 = false, const void* xb = nullptr,
                      const void* dyb = nullptr);
 long long conv_ws_floats(const ConvShape& s, bool fwd_epilogue);
+// The kernel the launchers above pick for a shape (read-only; tests assert
+// it so that a plan change cannot move a case onto another kernel unseen).
+// op: 0 forward, 1 backward-data, 2 backward-filter.  bf16: bf16 conv mode
+// with the bf16 operand copies present (as ops/functional.py always passes
+// them).  epilogue: a bias / ReLU forward.  wcopy: the fp32 stride-1 dgrad
+// weight copy is passed (fp32 forward only).  stem: 0 = the shape goes through
+// conv_fwd / conv_bwd_data / conv_bwd_filter; 1 = s is the 1x1 GEMM view of
+// conv_fwd_stem_bf16 / conv_bwd_filter_stem_bf16; 2 = s is the 4x4 conv of
+// conv_fwd_s2d_stem_bf16 / conv_bwd_filter_s2d_stem_bf16.
+struct ConvRoute {
+  const char* family = "";  // "bf16" | "tiled" | "direct" | "gather"
+  const char* kernel = "";
+  int bm = 0, bn = 0;       // block tile (rows x columns of the kernel's GEMM)
+  int z = 1;                // split-K slabs
+  bool halo = false, stem = false;
+};
+ConvRoute conv_route(const ConvShape& s, int op, bool bf16, bool epilogue, bool wcopy, int stem);
+ConvRoute conv_route_bf16(const ConvShape& s, int op, bool epilogue, int stem);
+ConvRoute conv_route_tiled(const ConvShape& s, int op, bool bf16, bool epilogue, bool wcopy);
 // bf16 MFMA convs with 64-channel K tiles and pre-laid-out bf16 weights
 // (conv_bf16.hip): forward for C, K % 64 == 0, stride-1 backward-data; the
 // bf16 weight copy and split-K slabs live in the layer workspace

@@ -1205,6 +1205,45 @@ void conv_bwd_filter(const ConvShape& s, const float* x, const float* dy, float*
     slab_sum_kernel<<<grid1d(n), 256, 0, st>>>(part, zz, n, dw);
 }
 
+// follows conv_fwd / conv_bwd_data / conv_bwd_filter above (without BatchNorm
+// statistics, which the fp32 forward sends to the tiled kernels regardless)
+ConvRoute conv_route(const ConvShape& s, int op, bool bf16, bool epilogue, bool wcopy, int stem) {
+  if (op < 0 || op > 2) throw std::runtime_error("conv_route: op must be 0 (fwd), 1 (dgrad), 2 (wgrad)");
+  if (stem) return conv_route_bf16(s, op, epilogue, stem);
+  ConvRoute r;
+  if (op == 0) {
+    if (bf16 && conv_fwd_bf16_ok(s)) return conv_route_bf16(s, op, epilogue, 0);
+    if (!bf16 && wcopy && !epilogue && conv3f_ok(s)) return conv_route_tiled(s, op, bf16, epilogue, wcopy);
+    if (conv_fwd_tiled_ok(s)) return conv_route_tiled(s, op, bf16, epilogue, false);
+    if (conv_fwd_direct_ok(s)) {
+      r.family = "direct", r.kernel = "conv_fwd_direct_kernel";
+      return r;
+    }
+    if (!bf16 && conv_fwd_tiled_gather_ok(s)) return conv_route_tiled(s, op, false, epilogue, false);
+    r.family = "gather", r.kernel = "conv_fwd_kernel", r.bm = CFG_F::BM, r.bn = CFG_F::BN;
+    return r;
+  }
+  if (op == 1) {
+    if (bf16 && conv_bwd_data_bf16_ok(s)) return conv_route_bf16(s, op, false, 0);
+    if (conv_bwd_data_tiled_ok(s)) return conv_route_tiled(s, op, bf16, false, wcopy);
+    if (s.C < 32 && (long long)s.R * s.S * s.C * s.K <= DIRECT_W_MAX && (s.K == 8 || s.K == 16)) {
+      r.family = "direct", r.kernel = "conv_bwd_data_direct_kernel";
+      return r;
+    }
+    int kchunk;
+    gather_data_plan(s, r.z, kchunk);
+    r.family = "gather", r.kernel = "conv_bwd_data_kernel", r.bm = CFG_D::BM, r.bn = CFG_D::BN;
+    return r;
+  }
+  if (bf16 && conv_bwd_filter_bf16_ok(s)) return conv_route_bf16(s, op, false, 0);
+  if (conv_bwd_filter_tiled_ok(s)) return conv_route_tiled(s, op, bf16, false, false);
+  const int ktiles = (s.N * s.OH * s.OW + BK - 1) / BK;
+  const int kchunk = ((ktiles + conv_filter_splits(s) - 1) / conv_filter_splits(s)) * BK;
+  r.family = "gather", r.kernel = "conv_bwd_filter_kernel", r.bm = CFG_W::BM, r.bn = CFG_W::BN;
+  r.z = (ktiles * BK + kchunk - 1) / kchunk;
+  return r;
+}
+
 void colsum2(const float* a, const float* b, long long rows, int C, float* s1, float* s2, int mode,
              float* ws, hipStream_t st) {
   // deterministic two-pass reduction (bn.hip); the memset + atomic kernel
