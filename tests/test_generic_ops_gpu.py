@@ -109,7 +109,7 @@ def test_batchnorm(cuda_dev, relu, res):
     assert torch.allclose(rm.cpu(), 0.1 * x.mean(dim=(0, 1, 2)), atol=1e-5)
 
 
-@pytest.mark.parametrize("C", [10, 16])  # scalar and float4 kernels
+@pytest.mark.parametrize("C", [10, 16])  # scalar int32-tap kernels; C % 4 == 0: the uint8-tap float4 kernels
 @pytest.mark.parametrize("k,stride,pad,H", [(2, 2, 0, 12), (3, 2, 1, 13)])
 def test_maxpool(cuda_dev, k, stride, pad, H, C):
     g = torch.Generator().manual_seed(2)
