@@ -661,24 +661,33 @@ PYBIND11_MODULE(_C, m) {
   });
   g.def("conv_ws_floats", &gops::conv_ws_floats);
   g.def("conv_filter_splits", &gops::conv_filter_splits);
-  // read-only: the kernel family, tile, split count and halo / stem path the
-  // launchers take for a shape (gops::conv_route)
+  // read-only: the plan the launchers execute for a call (gops::conv_route) -
+  // kernel family and name, tile, K-tile depth, split count, halo / stem path,
+  // workspace floats and statistics rows.  The keyword flags say what the call
+  // provides (gops::ConvHave); act16: xb for fwd / wgrad, dyb for dgrad
   g.def("conv_route", [](const gops::ConvShape& s, const std::string& op, bool bf16, bool epilogue,
-                         bool wcopy, int stem) {
+                         bool wcopy, int stem, bool act16, bool dy16, bool dy32, bool ws, bool stats) {
     const int o = op == "fwd" ? 0 : op == "dgrad" ? 1 : op == "wgrad" ? 2 : -1;
     if (o < 0) throw std::runtime_error("conv_route: op must be fwd | dgrad | wgrad");
-    const gops::ConvRoute r = gops::conv_route(s, o, bf16, epilogue, wcopy, stem);
+    const gops::ConvHave h{epilogue, act16, dy16, dy32, wcopy, ws, stats};
+    const gops::ConvRoute r = gops::conv_route(s, o, bf16, h, stem);
     py::dict d;
     d["family"] = std::string(r.family);
     d["kernel"] = std::string(r.kernel);
-    d["bm"] = r.bm;
-    d["bn"] = r.bn;
-    d["z"] = r.z;
-    d["halo"] = r.halo;
-    d["stem"] = r.stem;
+    d["bm"] = r.plan.bm;
+    d["bn"] = r.plan.bn;
+    d["z"] = r.plan.z;
+    d["halo"] = r.plan.halo;
+    d["stem"] = r.plan.stem;
+    d["bk"] = r.plan.bk;
+    d["ws_floats"] = r.plan.ws_floats;
+    d["stats_rows"] = r.plan.stats_rows;
+    d["addend_ok"] = r.plan.addend_ok;
     return d;
   }, py::arg("shape"), py::arg("op"), py::arg("bf16"), py::arg("epilogue") = false,
-     py::arg("wcopy") = false, py::arg("stem") = 0);
+     py::arg("wcopy") = false, py::arg("stem") = 0, py::arg("act16") = true,
+     py::arg("dy16") = true, py::arg("dy32") = true, py::arg("ws") = true,
+     py::arg("stats") = false);
   g.def("conv_bwd_filter", [](const gops::ConvShape& s, uintptr_t x, uintptr_t dy, uintptr_t part,
                               uintptr_t dw, uintptr_t st, bool bf16, uintptr_t xb, uintptr_t dyb) {
     gops::conv_bwd_filter(s, P<const float>(x), P<const float>(dy), P<float>(part), P<float>(dw),

@@ -1751,14 +1751,35 @@ static void slab_reduce(float* slabs, int nz, long long n4, float* out, hipStrea
 enum Tile { T128x128, T128x64, T64x128, T64x64 };
 static inline int tm(Tile t) { return (t == T128x128 || t == T128x64) ? 128 : 64; }
 static inline int tn(Tile t) { return (t == T128x128 || t == T64x128) ? 128 : 64; }
+// X(bm, bn) instantiated on the four tiles, run on the plan's
+#define TILE_DISPATCH(p, X)                        \
+  do {                                             \
+    if (p.bm == 128 && p.bn == 128) X(128, 128);   \
+    else if (p.bm == 128) X(128, 64);              \
+    else if (p.bn == 128) X(64, 128);              \
+    else X(64, 64);                                \
+  } while (0)
+
+static inline long long wt_elems(const ConvShape& s) { return (long long)s.R * s.S * s.C * s.K; }
+// bf16 weight copy at the front of the workspace, split-K slabs after it
+static inline long long wt_floats(const ConvShape& s) { return ((wt_elems(s) + 127) / 128) * 64; }
+
+// a plan of the kernels that read the bf16 weight copy: z slabs of `out`
+// floats behind it; rows: the statistics rows of an unsplit launch (the slab
+// reduction's otherwise)
+static inline ConvPlan new_plan(ConvKernel k, const ConvShape& s, int bm, int bn, int z, int per,
+                                long long out, int rows) {
+  ConvPlan p;
+  p.kernel = k, p.run = s, p.bm = bm, p.bn = bn, p.bk = BK, p.z = z, p.per = per;
+  p.slabs = wt_floats(s);
+  p.ws_floats = p.slabs + (z > 1 ? z * out : 0);
+  p.stats_rows = z > 1 ? slab_blocks(out / 4) : rows;
+  return p;
+}
 
 // Largest tile that still gives >= 256 blocks (one per CU); deep layers that
 // cannot reach it take 64x64 (or 64x128) tiles plus split-K.
-struct Plan {
-  Tile t;
-  int z, kps;
-};
-static inline Plan plan(const ConvShape& s, bool epilogue) {
+static inline ConvPlan plan(const ConvShape& s, bool epilogue, ConvKernel k = ConvKernel::B16_FWD) {
   const long long M = (long long)s.N * s.OH * s.OW;
   const Tile order[4] = {T128x128, T128x64, T64x128, T64x64};
   Tile t = T64x64;
@@ -1781,47 +1802,35 @@ static inline Plan plan(const ConvShape& s, bool epilogue) {
     if (z < 1) z = 1;
   }
   const int kps = cdiv(nk, z);
-  return {t, cdiv(nk, kps), kps};
+  ConvPlan p = new_plan(k, s, tm(t), tn(t), cdiv(nk, kps), kps, M * s.K, cdiv(M, tm(t)) * 2);
+  if (epilogue) p.stats_rows = 0;  // statistics need a plain conv
+  return p;
 }
 
-static inline long long wt_elems(const ConvShape& s) { return (long long)s.R * s.S * s.C * s.K; }
-// bf16 weight copy at the front of the workspace, split-K slabs after it
-static inline long long wt_floats(const ConvShape& s) { return ((wt_elems(s) + 127) / 128) * 64; }
-
-// partial rows of the BatchNorm statistics the forward writes (plan-dependent)
-static int stats_rows(const ConvShape& s, bool epilogue) {
-  const long long M = (long long)s.N * s.OH * s.OW;
-  const Plan p = plan(s, epilogue);
-  if (p.z > 1) return slab_blocks(M * s.K / 4);
-  return cdiv(M, tm(p.t)) * 2;
-}
-
+// fwd_kernel on p.run (B16_FWD, B16_FWD_EX2)
 template <class XT>
-static void launch(const ConvShape& s, const XT* x, const __bf16* wt, const float* bias,
-                   float* y, bool relu, float* ws, hipStream_t st,
-                   const float* addend = nullptr, __bf16* yb = nullptr, int ex2 = 0,
-                   const ConvStats* stats = nullptr) {
+static void launch(const ConvPlan& p, const XT* x, const __bf16* wt, const float* bias, float* y,
+                   bool relu, float* ws, hipStream_t st, const float* addend = nullptr,
+                   __bf16* yb = nullptr, const ConvStats* stats = nullptr) {
+  const ConvShape& s = p.run;
   const long long M = (long long)s.N * s.OH * s.OW;
-  const Plan p = plan(s, bias != nullptr || relu || ex2);  // ex2: never split
+  const int ex2 = p.kernel == ConvKernel::B16_FWD_EX2;
   ConvStats cs;
   if (stats && stats->part) {
-    if (!yb || bias || relu || ex2 || stats->P != stats_rows(s, false))
+    if (!yb || p.stats_rows == 0 || stats->P != p.stats_rows)
       throw std::runtime_error("conv fwd: BatchNorm statistics need a plain bf16-output conv");
     if (p.z == 1) cs = *stats;
   }
-  float* slabs = ws + wt_floats(s);
+  float* slabs = ws + p.slabs;
   float* out = p.z > 1 ? slabs : y;
   const float* add = p.z > 1 ? nullptr : addend;  // split-K: added by the slab reduction
   __bf16* ob = p.z > 1 ? nullptr : yb;             // ... and converted there
   const int r = relu ? 1 : 0;
-#define GRID(BM_, BN_) dim3(cdiv(M, BM_) * cdiv(s.K, BN_), p.z)
-  switch (p.t) {
-    case T128x128: fwd_kernel<128, 128, XT><<<GRID(128, 128), NT, 0, st>>>(s, x, wt, bias, out, r, p.kps, add, ob, ex2, s, cs); break;
-    case T128x64: fwd_kernel<128, 64, XT><<<GRID(128, 64), NT, 0, st>>>(s, x, wt, bias, out, r, p.kps, add, ob, ex2, s, cs); break;
-    case T64x128: fwd_kernel<64, 128, XT><<<GRID(64, 128), NT, 0, st>>>(s, x, wt, bias, out, r, p.kps, add, ob, ex2, s, cs); break;
-    default: fwd_kernel<64, 64, XT><<<GRID(64, 64), NT, 0, st>>>(s, x, wt, bias, out, r, p.kps, add, ob, ex2, s, cs); break;
-  }
-#undef GRID
+#define FWD(BM_, BN_)                                                                          \
+  fwd_kernel<BM_, BN_, XT><<<dim3(cdiv(M, BM_) * cdiv(s.K, BN_), p.z), NT, 0, st>>>(s, x, wt, bias, \
+      out, r, p.per, add, ob, ex2, s, cs)
+  TILE_DISPATCH(p, FWD);
+#undef FWD
   if (p.z > 1) slab_reduce(slabs, p.z, M * s.K / 4, y, st, addend, yb, stats, s.K);
 }
 
@@ -1832,56 +1841,53 @@ static bool conv3_ok(const ConvShape& s) {
          s.C % 64 == 0 && s.K % 64 == 0 && h3::halo_rows(s, 128) <= h3::HCAP &&
          (long long)s.N * s.H * s.W * s.C < (1LL << 31);
 }
-// 64-channel output tiles; split-K over channel chunks up to one block per CU
-struct P3 {
-  int z, cps, bm;
-};
+// 64-channel output tiles; split-K over channel chunks up to one block per CU:
 // 128-pixel tiles when they fill the chip; otherwise (the small-M deep
 // layers) 64-pixel tiles, split-K over channel chunks only below 128 blocks
 // (split-K slabs cost a ~7 us reduction launch per conv)
-static inline P3 plan3(const ConvShape& s) {
+static inline ConvPlan plan3(const ConvShape& s) {
   const long long M = (long long)s.N * s.H * s.W;
   const int nch = s.C / BK;
-  if ((long long)cdiv(M, 128) * (s.K / 64) >= 256) return {1, nch, 128};
-  const long long blocks = (long long)cdiv(M, 64) * (s.K / 64);
-  int z = 1;
-  if (blocks < 128) {
-    z = cdiv(256, blocks);
-    if (z > nch) z = nch;
+  int z = 1, bm = 128;
+  if ((long long)cdiv(M, 128) * (s.K / 64) < 256) {
+    bm = 64;
+    const long long blocks = (long long)cdiv(M, 64) * (s.K / 64);
+    if (blocks < 128) {
+      z = cdiv(256, blocks);
+      if (z > nch) z = nch;
+    }
   }
   const int cps = cdiv(nch, z);
-  return {cdiv(nch, cps), cps, 64};
+  ConvPlan p = new_plan(ConvKernel::B16_CONV3, s, bm, 64, cdiv(nch, cps), cps, M * s.K,
+                        cdiv(M, bm) * 2);
+  p.halo = true;
+  return p;
 }
-static int stats_rows3(const ConvShape& s) {
-  const long long M = (long long)s.N * s.H * s.W;
-  const P3 p = plan3(s);
-  if (p.z > 1) return slab_blocks(M * s.K / 4);
-  return cdiv(M, p.bm) * 2;
-}
-static void launch3(const ConvShape& s, const __bf16* x, const __bf16* wt, float* y, float* ws,
+// conv3_kernel on p.run
+static void launch3(const ConvPlan& p, const __bf16* x, const __bf16* wt, float* y, float* ws,
                     hipStream_t st, const float* addend, __bf16* yb = nullptr,
                     const ConvStats* stats = nullptr, const BnBwdStats* bstats = nullptr) {
+  const ConvShape& s = p.run;
   const long long M = (long long)s.N * s.H * s.W;
-  const P3 p = plan3(s);
   ConvStats cs;
   if (stats && stats->part) {
-    if (!yb || addend || stats->P != stats_rows3(s))
+    if (!yb || addend || stats->P != p.stats_rows)
       throw std::runtime_error("conv3: BatchNorm statistics need a plain bf16-output conv");
     if (p.z == 1) cs = *stats;
   }
   BnBwdStats bb;
   if (bstats && bstats->part) {
-    if (yb || bstats->P != stats_rows3(s))
+    if (yb || bstats->P != p.stats_rows)
       throw std::runtime_error("conv3: BatchNorm backward statistics layout mismatch");
     if (p.z == 1) bb = *bstats;
   }
-  float* slabs = ws + wt_floats(s);
+  float* slabs = ws + p.slabs;
   float* out = p.z > 1 ? slabs : y;
   const dim3 grid(cdiv(M, p.bm) * (s.K / 64), p.z);
   const float* add = p.z > 1 ? nullptr : addend;
   __bf16* ob = p.z > 1 ? nullptr : yb;
   const int epi = ob ? 1 : (bb.part ? 2 : 0);
-#define C3(BM_, E_) conv3_kernel<BM_, 64, 4, E_><<<grid, NT, 0, st>>>(s, x, wt, out, p.cps, add, ob, cs, bb)
+#define C3(BM_, E_) conv3_kernel<BM_, 64, 4, E_><<<grid, NT, 0, st>>>(s, x, wt, out, p.per, add, ob, cs, bb)
   if (p.bm == 128) {
     if (epi == 1) C3(128, 1); else if (epi == 2) C3(128, 2); else C3(128, 0);
   } else {
@@ -1899,8 +1905,10 @@ static bool dgrad3s2_ok(const ConvShape& s) {
          (long long)s.N * s.H * s.W * s.C < (1LL << 31);
 }
 // split-K over co chunks up to one block per CU (measured: splitting only
-// below 128 blocks - fewer 4x-sized dX slabs - was no faster, 2.70 vs 2.69 ms)
-static inline P3 plan3s2(const ConvShape& s) {
+// below 128 blocks - fewer 4x-sized dX slabs - was no faster, 2.70 vs 2.69 ms).
+// 64-pixel tiles: with four accumulator classes a 128-pixel tile needed 272
+// registers a lane (one wave per SIMD) and ran 10x slower per tile
+static inline ConvPlan plan3s2(const ConvShape& s) {
   const long long M = (long long)s.N * s.OH * s.OW;
   const long long blocks = (long long)cdiv(M, 64) * (s.C / 64);
   const int nch = s.K / BK;
@@ -1910,32 +1918,25 @@ static inline P3 plan3s2(const ConvShape& s) {
     if (z > nch) z = nch;
   }
   const int cps = cdiv(nch, z);
-  return {cdiv(nch, cps), cps, 64};
+  ConvPlan p = new_plan(ConvKernel::B16_DGRAD3S2, s, 64, 64, cdiv(nch, cps), cps,
+                        (long long)s.N * s.H * s.W * s.C, cdiv(M, 64) * 2);
+  p.halo = true;
+  return p;
 }
-// partial rows of the BatchNorm backward statistics launch3s2 writes
-static int stats_rows3s2(const ConvShape& s) {
+static void launch3s2(const ConvPlan& p, const __bf16* dy, const __bf16* wt, float* dx, float* ws,
+                      hipStream_t st, const float* addend, const BnBwdStats* bstats = nullptr) {
+  const ConvShape& s = p.run;
   const long long M = (long long)s.N * s.OH * s.OW;
-  const P3 p = plan3s2(s);
-  if (p.z > 1) return slab_blocks((long long)s.N * s.H * s.W * s.C / 4);
-  return cdiv(M, 64) * 2;
-}
-static void launch3s2(const ConvShape& s, const __bf16* dy, const __bf16* wt, float* dx,
-                      float* ws, hipStream_t st, const float* addend,
-                      const BnBwdStats* bstats = nullptr) {
-  const long long M = (long long)s.N * s.OH * s.OW;
-  const P3 p = plan3s2(s);
   BnBwdStats bb;
   if (bstats && bstats->part) {
-    if (bstats->P != stats_rows3s2(s))
+    if (bstats->P != p.stats_rows)
       throw std::runtime_error("dgrad3s2: BatchNorm backward statistics layout mismatch");
     if (p.z == 1) bb = *bstats;
   }
-  float* slabs = ws + wt_floats(s);
+  float* slabs = ws + p.slabs;
   float* out = p.z > 1 ? slabs : dx;
-  // 64-pixel tiles: with four accumulator classes a 128-pixel tile needed 272
-  // registers a lane (one wave per SIMD) and ran 10x slower per tile
   const dim3 grid(cdiv(M, 64) * (s.C / 64), p.z);
-  dgrad3s2_kernel<64, 64, 4><<<grid, NT, 0, st>>>(s, dy, wt, out, p.cps,
+  dgrad3s2_kernel<64, 64, 4><<<grid, NT, 0, st>>>(s, dy, wt, out, p.per,
                                                   p.z > 1 ? nullptr : addend, bb);
   if (p.z > 1)
     slab_reduce(slabs, p.z, (long long)s.N * s.H * s.W * s.C / 4, dx, st, addend, nullptr,
@@ -1944,10 +1945,7 @@ static void launch3s2(const ConvShape& s, const __bf16* dy, const __bf16* wt, fl
 
 // wgrad: tile = (ci, co) per tap; pixel slices fill the chip (~1024 blocks),
 // at least 4 K tiles per slice, at most 64 slices
-struct WgPlan {
-  int bm, bn, z, kchunk;
-};
-static inline WgPlan wg_plan(const ConvShape& s) {
+static inline ConvPlan wg_plan(const ConvShape& s) {
   // (128-row tiles on the space-to-depth stem's 16 taps x 16 channels, each dY
   // tile feeding 8 taps: its filter gradient 69.2 -> 72.4 us, step neutral;
   // r6_s40.steps)
@@ -1965,7 +1963,11 @@ static inline WgPlan wg_plan(const ConvShape& s) {
   if (z > zcap) z = zcap;
   if (z < 1) z = 1;
   const int kchunk = cdiv(ktiles, z);
-  return {bm, bn, cdiv(ktiles, kchunk), kchunk};
+  ConvPlan p;
+  p.kernel = ConvKernel::B16_WGRAD, p.run = s, p.bm = bm, p.bn = bn, p.bk = BK;
+  p.z = cdiv(ktiles, kchunk), p.per = kchunk;
+  p.ws_floats = p.z > 1 ? p.z * wt_elems(s) : 0;
+  return p;
 }
 
 static void convert(const ConvShape& s, const float* w, int mode, __bf16* out, hipStream_t st) {
@@ -2228,28 +2230,29 @@ static int wgrad3_chunks(const ConvShape& s) {
 // per call at 19 MB, but halving the splits to that leaves the per-block
 // chunk chains (load -> 9 x 4 MFMAs -> barrier) too long: 607 vs 489 us per
 // step for the 13 layers; 76 MB: 681 us.
-static int wgrad3_splits(const ConvShape& s) {
+static ConvPlan wgrad3_plan(const ConvShape& s) {
   const int nchunks = wgrad3_chunks(s);
   const long long budget = 9437184LL;
   long long z = (budget + 9LL * s.C * s.K - 1) / (9LL * s.C * s.K);
   z = std::max(1LL, std::min(z, (long long)nchunks));
   const int cps = (int)((nchunks + z - 1) / z);
-  return (nchunks + cps - 1) / cps;
+  ConvPlan p;
+  p.kernel = ConvKernel::B16_WGRAD3, p.run = s, p.bm = w3::chunk_pixels(s), p.bn = 64, p.bk = 16;
+  p.z = (nchunks + cps - 1) / cps, p.per = (nchunks + p.z - 1) / p.z, p.halo = true;
+  p.ws_floats = p.z > 1 ? p.z * wt_elems(s) : 0;
+  return p;
 }
 
-static void wgrad3(const ConvShape& s, const __bf16* xb, const __bf16* dyb, float* ws, float* dw,
+static void wgrad3(const ConvPlan& p, const __bf16* xb, const __bf16* dyb, float* ws, float* dw,
                    hipStream_t st) {
-  const int nchunks = wgrad3_chunks(s);
-  const int z = wgrad3_splits(s);
-  const int cps = (nchunks + z - 1) / z;
-  const int blocks = (s.C / 64) * (s.K / 64) * z;
-  if (z > 1 && !ws) throw std::runtime_error("wgrad3: split-K needs a workspace");
-  float* out = z > 1 ? ws : dw;
-  if (w3::chunk_pixels(s) == 128)
-    wgrad3_kernel<128><<<blocks, NT, 0, st>>>(s, xb, dyb, out, cps);
+  const ConvShape& s = p.run;
+  const int blocks = (s.C / 64) * (s.K / 64) * p.z;
+  float* out = p.z > 1 ? ws : dw;
+  if (p.bm == 128)
+    wgrad3_kernel<128><<<blocks, NT, 0, st>>>(s, xb, dyb, out, p.per);
   else
-    wgrad3_kernel<64><<<blocks, NT, 0, st>>>(s, xb, dyb, out, cps);
-  if (z > 1) slab_reduce(ws, z, 9LL * s.C * s.K / 4, dw, st);
+    wgrad3_kernel<64><<<blocks, NT, 0, st>>>(s, xb, dyb, out, p.per);
+  if (p.z > 1) slab_reduce(ws, p.z, 9LL * s.C * s.K / 4, dw, st);
 }
 
 }  // namespace cbf
@@ -2268,33 +2271,23 @@ bool conv_bwd_data_bf16_ok(const ConvShape& s) {
           s.OH == s.H + 2 * s.pad - s.R + 1 && s.OW == s.W + 2 * s.pad - s.S + 1);
 }
 
+// workspace for every kernel of this file that may take s: the calls of a
+// layer share one workspace, and which operand copies they pass (so the halo
+// or the GEMM kernel) is not known when it is built
 long long conv_bf16_ws_floats(const ConvShape& s, bool fwd_epilogue) {
   using namespace cbf;
   long long n = 0;
-  auto slab_floats = [](const ConvShape& c, bool epi) {
-    const Plan p = plan(c, epi);
-    const long long mk = (long long)c.N * c.OH * c.OW * c.K;
-    long long f = p.z > 1 ? p.z * mk : 0LL;
-    if (conv3_ok(c)) {
-      const P3 q = plan3(c);
-      if (q.z > 1) f = std::max(f, q.z * mk);
-    }
-    return f;
+  auto fwd_floats = [](const ConvShape& c, bool epi) {
+    const long long f = plan(c, epi).ws_floats;
+    return conv3_ok(c) ? std::max(f, plan3(c).ws_floats) : f;
   };
-  if (conv_fwd_bf16_ok(s)) n = std::max(n, wt_floats(s) + slab_floats(s, fwd_epilogue));
+  if (conv_fwd_bf16_ok(s)) n = std::max(n, fwd_floats(s, fwd_epilogue));
   if (conv_bwd_data_bf16_ok(s)) {
-    const ConvShape d = dgrad_shape(s);
-    n = std::max(n, wt_floats(d) + slab_floats(d, false));
-    if (dgrad3s2_ok(s)) {
-      const P3 q = plan3s2(s);
-      if (q.z > 1) n = std::max(n, wt_floats(s) + (long long)q.z * s.N * s.H * s.W * s.C);
-    }
+    n = std::max(n, fwd_floats(dgrad_shape(s), false));
+    if (dgrad3s2_ok(s)) n = std::max(n, plan3s2(s).ws_floats);
   }
-  if (conv_bwd_filter_bf16_ok(s)) {
-    const WgPlan p = wg_plan(s);
-    if (p.z > 1) n = std::max(n, (long long)p.z * s.R * s.S * s.C * s.K);
-  }
-  if (wgrad3_ok(s)) n = std::max(n, (long long)wgrad3_splits(s) * 9 * s.C * s.K);
+  if (conv_bwd_filter_bf16_ok(s)) n = std::max(n, wg_plan(s).ws_floats);
+  if (wgrad3_ok(s)) n = std::max(n, wgrad3_plan(s).ws_floats);
   return n;
 }
 
@@ -2384,194 +2377,9 @@ void sgd_wcvt(float* w, const float* g, float* mom, float momentum, float gscale
   cbf::sgd_wcvt_kernel<<<(int)(conv_blocks + range_blocks), 256, 0, st>>>(a);
 }
 
-int conv_fwd_stats_rows(const ConvShape& s, bool bf16) {
-  using namespace cbf;
-  if (!bf16) {
-    if (!conv_fwd_tiled_ok(s) && !conv_fwd_tiled_gather_ok(s))
-      throw std::runtime_error("conv_fwd_stats_rows: not a tiled-family conv");
-    return conv_fwd_tiled_stats_rows(s, false);
-  }
-  if (!conv_fwd_bf16_ok(s)) throw std::runtime_error("conv_fwd_stats_rows: not a bf16-family conv");
-  return conv3_ok(s) ? stats_rows3(s) : stats_rows(s, false);
-}
-
 int conv_fwd_stem_stats_rows(const ConvShape& s1) {
   using namespace cbf;
   return cdiv((long long)s1.N * s1.OH * s1.OW, 128) * 2;
-}
-
-void conv_fwd_bf16(const ConvShape& s, const float* x, const float* w, const float* bias, float* y,
-                   bool relu, float* ws, hipStream_t st, const void* xb, const void* wtb,
-                   void* yb, const ConvStats* stats) {
-  using namespace cbf;
-  if (!conv_fwd_bf16_ok(s) || !ws) throw std::runtime_error("conv_fwd_bf16: unsupported shape");
-  const __bf16* wt = reinterpret_cast<const __bf16*>(wtb);
-  if (!wt) {
-    __bf16* wc = reinterpret_cast<__bf16*>(ws);
-    convert(s, w, 0, wc, st);
-    wt = wc;
-  }
-  __bf16* ob = reinterpret_cast<__bf16*>(yb);
-  // statistics rows are planned for the halo kernel whenever it takes the shape
-  if (stats && stats->part && conv3_ok(s) && !(xb && !bias && !relu))
-    throw std::runtime_error("conv_fwd_bf16: statistics need the bf16 input of a plain halo conv");
-  if (xb && !bias && !relu && conv3_ok(s))
-    launch3(s, reinterpret_cast<const __bf16*>(xb), wt, y, ws, st, nullptr, ob, stats);
-  else if (xb)
-    launch(s, reinterpret_cast<const __bf16*>(xb), wt, bias, y, relu, ws, st, nullptr, ob, 0, stats);
-  else
-    launch(s, x, wt, bias, y, relu, ws, st, nullptr, ob, 0, stats);
-}
-
-// BatchNorm backward statistics rows of the dgrad of s (0: not available -
-// the dgrad kinds without the epilogue, or a channel count the slab pass
-// cannot keep one quad per thread of)
-int conv_bwd_data_stats_rows(const ConvShape& s) {
-  using namespace cbf;
-  if (!conv_bwd_data_bf16_ok(s) || s.C % 64 != 0 || 256 % (s.C / 4) != 0) return 0;
-  if (dgrad3s2_ok(s)) return stats_rows3s2(s);
-  if (dgrad_1x1s2(s)) return 0;
-  if (conv3_ok(dgrad_shape(s))) return stats_rows3(dgrad_shape(s));
-  return 0;
-}
-
-void conv_bwd_data_bf16(const ConvShape& s, const float* dy, const float* w, float* dx, float* ws,
-                        hipStream_t st, const void* dyb, const float* addend, const void* wtb,
-                        const BnBwdStats* bstats) {
-  using namespace cbf;
-  if (!conv_bwd_data_bf16_ok(s) || !ws) throw std::runtime_error("conv_bwd_data_bf16: unsupported shape");
-  if (bstats && bstats->part &&
-      (!dyb || bstats->P != conv_bwd_data_stats_rows(s) || bstats->P == 0 || !bstats->x ||
-       !bstats->mean || !bstats->rstd || (bstats->relu && !bstats->y)))
-    throw std::runtime_error("conv_bwd_data_bf16: BatchNorm backward statistics not available here");
-  BnBwdStats bsv;
-  if (bstats && bstats->part) {  // the kernels load y unconditionally: y = x without a ReLU
-    bsv = *bstats;
-    if (!bsv.relu) bsv.y = bsv.x;
-    bstats = &bsv;
-  }
-  const __bf16* wt = reinterpret_cast<const __bf16*>(wtb);
-  if (!wt) {
-    __bf16* wc = reinterpret_cast<__bf16*>(ws);
-    convert(s, w, 1, wc, st);
-    wt = wc;
-  }
-  if (dgrad3s2_ok(s)) {
-    if (dyb)
-      return launch3s2(s, reinterpret_cast<const __bf16*>(dyb), wt, dx, ws, st, addend, bstats);
-    return conv_bwd_data_tiled(s, dy, w, dx, ws, st, true, addend);  // fp32 dY only
-  }
-  if (dgrad_1x1s2(s)) {  // a 1x1 GEMM over the dY pixels, 2x2-expanding epilogue
-    ConvShape d = dgrad_shape(s);
-    d.H = d.OH = s.OH;
-    d.W = d.OW = s.OW;
-    if (dyb)
-      launch(d, reinterpret_cast<const __bf16*>(dyb), wt, nullptr, dx, false, ws, st, addend,
-             nullptr, 1);
-    else
-      launch(d, dy, wt, nullptr, dx, false, ws, st, addend, nullptr, 1);
-    return;
-  }
-  if (dyb && conv3_ok(dgrad_shape(s)))
-    launch3(dgrad_shape(s), reinterpret_cast<const __bf16*>(dyb), wt, dx, ws, st, addend, nullptr,
-            nullptr, bstats);
-  else if (dyb)
-    launch(dgrad_shape(s), reinterpret_cast<const __bf16*>(dyb), wt, nullptr, dx, false, ws, st,
-           addend);
-  else
-    launch(dgrad_shape(s), dy, wt, nullptr, dx, false, ws, st, addend);
-}
-
-void conv_bwd_filter_bf16(const ConvShape& s, const float* x, const float* dy, float* ws,
-                          float* dw, hipStream_t st, const void* xb, const void* dyb) {
-  using namespace cbf;
-  if (!conv_bwd_filter_bf16_ok(s)) throw std::runtime_error("conv_bwd_filter_bf16: unsupported shape");
-  if (xb && dyb && wgrad3_ok(s))
-    return wgrad3(s, reinterpret_cast<const __bf16*>(xb), reinterpret_cast<const __bf16*>(dyb), ws,
-                  dw, st);
-  const WgPlan p = wg_plan(s);
-  if (p.z > 1 && !ws) throw std::runtime_error("conv_bwd_filter_bf16: split-K needs a workspace");
-  float* out = p.z > 1 ? ws : dw;
-  const int blocks = cdiv((long long)s.R * s.S * s.C, p.bm) * (s.K / p.bn) * p.z;
-  if (xb && dyb) {
-    const __bf16* xh = reinterpret_cast<const __bf16*>(xb);
-    const __bf16* dh = reinterpret_cast<const __bf16*>(dyb);
-    if (p.bm == 128 && p.bn == 128)
-      wgrad_kernel<128, 128, true><<<blocks, NT, 0, st>>>(s, xh, dh, out, p.kchunk, s);
-    else if (p.bm == 128)
-      wgrad_kernel<128, 64, true><<<blocks, NT, 0, st>>>(s, xh, dh, out, p.kchunk, s);
-    else if (p.bn == 128)
-      wgrad_kernel<64, 128, true><<<blocks, NT, 0, st>>>(s, xh, dh, out, p.kchunk, s);
-    else
-      wgrad_kernel<64, 64, true><<<blocks, NT, 0, st>>>(s, xh, dh, out, p.kchunk, s);
-  } else {
-    if (p.bm == 128 && p.bn == 128)
-      wgrad_kernel<128, 128, false><<<blocks, NT, 0, st>>>(s, x, dy, out, p.kchunk, s);
-    else if (p.bm == 128)
-      wgrad_kernel<128, 64, false><<<blocks, NT, 0, st>>>(s, x, dy, out, p.kchunk, s);
-    else if (p.bn == 128)
-      wgrad_kernel<64, 128, false><<<blocks, NT, 0, st>>>(s, x, dy, out, p.kchunk, s);
-    else
-      wgrad_kernel<64, 64, false><<<blocks, NT, 0, st>>>(s, x, dy, out, p.kchunk, s);
-  }
-  if (p.z > 1) slab_reduce(ws, p.z, (long long)s.R * s.S * s.C * s.K / 4, dw, st);
-}
-
-// ---- stem over the implicit im2col (StemLoader / StemWgLoader) ----------
-// s1: the 1x1 GEMM shape over kp channels (kp % 64 == 0, >= R * seg), si the
-// image conv (C * S <= seg, fp32 NHWC image x)
-static void stem_check(const ConvShape& s1, const ConvShape& si) {
-  const int seg = (si.S * si.C + 7) / 8 * 8;
-  if (s1.C % 64 || s1.C < si.R * seg || s1.K % 64 || s1.R != 1 || s1.S != 1 ||
-      s1.N != si.N || s1.OH != si.OH || s1.OW != si.OW ||
-      (long long)si.N * si.H * si.W * si.C >= (1LL << 31) ||
-      (long long)s1.N * s1.OH * s1.OW >= (1LL << 31))
-    throw std::runtime_error("stem conv: inconsistent shapes");
-}
-
-void conv_fwd_stem_bf16(const ConvShape& s1, const ConvShape& si, const float* x, const void* wtb,
-                        void* yb, hipStream_t st, const ConvStats* stats) {
-  using namespace cbf;
-  stem_check(s1, si);
-  const long long M = (long long)s1.N * s1.OH * s1.OW;
-  ConvStats cs;
-  if (stats && stats->part) {
-    if (stats->P != conv_fwd_stem_stats_rows(s1))
-      throw std::runtime_error("stem conv: BatchNorm statistics layout mismatch");
-    cs = *stats;
-  }
-  // 128 x 64 tiles: M = 401 K pixels at B = 32 (3136 blocks), no split.
-  // (An A operand built from an LDS halo of the block's image rows, staged
-  // once as bf16, measured 105 vs 90 us: the halo's 16 KB of LDS halved the
-  // blocks per CU and the chunk builds cost more than the L2 gathers saved.)
-  const dim3 grid(cdiv(M, 128) * (s1.K / 64), 1);
-  fwd_kernel<128, 64, float, StemLoader<128, 64>><<<grid, NT, 0, st>>>(
-      s1, x, reinterpret_cast<const __bf16*>(wtb), nullptr, nullptr, 0, s1.C / BK, nullptr,
-      reinterpret_cast<__bf16*>(yb), 0, si, cs);
-}
-
-void conv_bwd_filter_stem_bf16(const ConvShape& s1, const ConvShape& si, const float* x,
-                               const void* dyb, float* ws, float* dw, hipStream_t st) {
-  using namespace cbf;
-  stem_check(s1, si);
-  const WgPlan p = wg_plan(s1);
-  if (p.z > 1 && !ws) throw std::runtime_error("stem wgrad: split-K needs a workspace");
-  float* out = p.z > 1 ? ws : dw;
-  const int blocks = cdiv((long long)s1.C, p.bm) * (s1.K / p.bn) * p.z;
-  const __bf16* d = reinterpret_cast<const __bf16*>(dyb);
-#define STEM_WG(BM_, BN_)                                                                 \
-  wgrad_kernel<BM_, BN_, true, StemWgLoader<BM_, BN_>><<<blocks, NT, 0, st>>>(s1, x, d, out, \
-                                                                             p.kchunk, si)
-  if (p.bm == 128 && p.bn == 128)
-    STEM_WG(128, 128);
-  else if (p.bm == 128)
-    STEM_WG(128, 64);
-  else if (p.bn == 128)
-    STEM_WG(64, 128);
-  else
-    STEM_WG(64, 64);
-#undef STEM_WG
-  if (p.z > 1) slab_reduce(ws, p.z, (long long)s1.C * s1.K / 4, dw, st);
 }
 
 // ---- space-to-depth stem (S2dLoader) -----------------------------------
@@ -2595,31 +2403,212 @@ static void s2d_check(const ConvShape& si) {
 }
 
 static bool g_s2d_preload = true;  // A/B: S2dLoaderPre (all K tiles at once) vs S2dLoader
+void s2d_stem_set_preload(bool on) { g_s2d_preload = on; }
+
+// ------------------------------------------------------------ planners ----
+// The caller (plan_fwd / plan_dgrad / plan_wgrad, ops_generic.hip) has checked
+// the *_bf16_ok predicate of the op; the stem launchers plan for themselves.
+ConvPlan plan_fwd_bf16(const ConvShape& s, const ConvHave& h, int stem) {
+  using namespace cbf;
+  if (stem) {
+    // 128 x 64 tiles: M = 401 K pixels at B = 32 (3136 blocks), no split.
+    // (An A operand built from an LDS halo of the block's image rows, staged
+    // once as bf16, measured 105 vs 90 us: the halo's 16 KB of LDS halved the
+    // blocks per CU and the chunk builds cost more than the L2 gathers saved.)
+    if (stem == 2) s2d_check(s);
+    ConvPlan p;
+    p.kernel = stem != 2        ? ConvKernel::B16_STEM_FWD
+               : g_s2d_preload ? ConvKernel::B16_S2D_FWD_PRE
+                               : ConvKernel::B16_S2D_FWD;
+    p.run = stem == 2 ? s2d_gemm_shape(s) : s;
+    p.bm = 128, p.bn = 64, p.bk = BK, p.per = p.run.C / BK, p.stem = true;
+    p.stats_rows = conv_fwd_stem_stats_rows(p.run);
+    return p;
+  }
+  const bool halo = conv3_ok(s);
+  if (halo && h.act16 && !h.epilogue) return plan3(s);
+  ConvPlan p = plan(s, h.epilogue);
+  if (halo) p.stats_rows = 0;  // the rows are planned for the halo kernel whenever it takes the shape
+  return p;
+}
+
+// stats_rows: the BatchNorm backward statistics (0: a dgrad kind without the
+// epilogue, or a channel count the slab pass cannot keep one quad per thread of)
+ConvPlan plan_dgrad_bf16(const ConvShape& s, const ConvHave& h) {
+  using namespace cbf;
+  ConvPlan p;
+  if (dgrad3s2_ok(s)) {
+    if (!h.act16) return plan_dgrad_tiled(s, true, h);  // fp32 dY only: the tiled family
+    p = plan3s2(s);
+  } else if (dgrad_1x1s2(s)) {  // a 1x1 GEMM over the dY pixels, 2x2-expanding epilogue
+    ConvShape d = dgrad_shape(s);
+    d.H = d.OH = s.OH;
+    d.W = d.OW = s.OW;
+    p = plan(d, true, ConvKernel::B16_FWD_EX2);  // never split
+  } else if (h.act16 && conv3_ok(dgrad_shape(s))) {
+    p = plan3(dgrad_shape(s));
+  } else {
+    p = plan(dgrad_shape(s), false);
+    p.stats_rows = 0;
+  }
+  if (256 % (s.C / 4) != 0) p.stats_rows = 0;
+  return p;
+}
+
+ConvPlan plan_wgrad_bf16(const ConvShape& s, const ConvHave& h, int stem) {
+  using namespace cbf;
+  if (!stem && h.act16 && h.dy16 && wgrad3_ok(s)) return wgrad3_plan(s);
+  ConvPlan p = wg_plan(s);
+  if (stem == 1) p.kernel = ConvKernel::B16_STEM_WGRAD;
+  p.stem = stem != 0;
+  return p;
+}
+
+size_t s2d_stem_ws_floats(const ConvShape& si) {
+  s2d_check(si);
+  return (size_t)plan_wgrad_bf16(si, ConvHave(), 2).ws_floats;
+}
+
+// ----------------------------------------------------------- launchers ----
+void conv_fwd_bf16(const ConvPlan& p, const float* x, const float* w, const float* bias, float* y,
+                   bool relu, float* ws, hipStream_t st, const void* xb, const void* wtb, void* yb,
+                   const ConvStats* stats) {
+  using namespace cbf;
+  const __bf16* wt = reinterpret_cast<const __bf16*>(wtb);
+  if (!wt) {
+    __bf16* wc = reinterpret_cast<__bf16*>(ws);
+    convert(p.run, w, 0, wc, st);
+    wt = wc;
+  }
+  __bf16* ob = reinterpret_cast<__bf16*>(yb);
+  if (p.kernel == ConvKernel::B16_CONV3)
+    launch3(p, reinterpret_cast<const __bf16*>(xb), wt, y, ws, st, nullptr, ob, stats);
+  else if (xb)
+    launch(p, reinterpret_cast<const __bf16*>(xb), wt, bias, y, relu, ws, st, nullptr, ob, stats);
+  else
+    launch(p, x, wt, bias, y, relu, ws, st, nullptr, ob, stats);
+}
+
+void conv_bwd_data_bf16(const ConvPlan& p, const ConvShape& s, const float* dy, const float* w,
+                        float* dx, float* ws, hipStream_t st, const void* dyb, const float* addend,
+                        const void* wtb, const BnBwdStats* bstats) {
+  using namespace cbf;
+  if (bstats && bstats->part &&
+      (!dyb || bstats->P != p.stats_rows || bstats->P == 0 || !bstats->x || !bstats->mean ||
+       !bstats->rstd || (bstats->relu && !bstats->y)))
+    throw std::runtime_error("conv_bwd_data_bf16: BatchNorm backward statistics not available here");
+  BnBwdStats bsv;
+  if (bstats && bstats->part) {  // the kernels load y unconditionally: y = x without a ReLU
+    bsv = *bstats;
+    if (!bsv.relu) bsv.y = bsv.x;
+    bstats = &bsv;
+  }
+  const __bf16* wt = reinterpret_cast<const __bf16*>(wtb);
+  if (!wt) {
+    __bf16* wc = reinterpret_cast<__bf16*>(ws);
+    convert(s, w, 1, wc, st);
+    wt = wc;
+  }
+  const __bf16* d16 = reinterpret_cast<const __bf16*>(dyb);
+  if (p.kernel == ConvKernel::B16_DGRAD3S2)
+    launch3s2(p, d16, wt, dx, ws, st, addend, bstats);
+  else if (p.kernel == ConvKernel::B16_CONV3)
+    launch3(p, d16, wt, dx, ws, st, addend, nullptr, nullptr, bstats);
+  else if (d16)
+    launch(p, d16, wt, nullptr, dx, false, ws, st, addend);
+  else
+    launch(p, dy, wt, nullptr, dx, false, ws, st, addend);
+}
+
+// wgrad_kernel on the plan's tile: bf16 operands (xb, dyb) when both are
+// given, else fp32 ones converted in registers
+void conv_bwd_filter_bf16(const ConvPlan& p, const float* x, const float* dy, float* ws, float* dw,
+                          hipStream_t st, const void* xb, const void* dyb) {
+  using namespace cbf;
+  const ConvShape& s = p.run;
+  const __bf16* xh = reinterpret_cast<const __bf16*>(xb);
+  const __bf16* dh = reinterpret_cast<const __bf16*>(dyb);
+  if (p.kernel == ConvKernel::B16_WGRAD3) return wgrad3(p, xh, dh, ws, dw, st);
+  float* out = p.z > 1 ? ws : dw;
+  const int blocks = cdiv((long long)s.R * s.S * s.C, p.bm) * (s.K / p.bn) * p.z;
+#define WG_B16(BM_, BN_) wgrad_kernel<BM_, BN_, true><<<blocks, NT, 0, st>>>(s, xh, dh, out, p.per, s)
+#define WG_F32(BM_, BN_) wgrad_kernel<BM_, BN_, false><<<blocks, NT, 0, st>>>(s, x, dy, out, p.per, s)
+  if (xb && dyb) {
+    TILE_DISPATCH(p, WG_B16);
+  } else {
+    TILE_DISPATCH(p, WG_F32);
+  }
+#undef WG_B16
+#undef WG_F32
+  if (p.z > 1) slab_reduce(ws, p.z, (long long)s.R * s.S * s.C * s.K / 4, dw, st);
+}
+
+// ---- stem over the implicit im2col (StemLoader / StemWgLoader) ----------
+// s1: the 1x1 GEMM shape over kp channels (kp % 64 == 0, >= R * seg), si the
+// image conv (C * S <= seg, fp32 NHWC image x)
+static void stem_check(const ConvShape& s1, const ConvShape& si) {
+  const int seg = (si.S * si.C + 7) / 8 * 8;
+  if (s1.C % 64 || s1.C < si.R * seg || s1.K % 64 || s1.R != 1 || s1.S != 1 ||
+      s1.N != si.N || s1.OH != si.OH || s1.OW != si.OW ||
+      (long long)si.N * si.H * si.W * si.C >= (1LL << 31) ||
+      (long long)s1.N * s1.OH * s1.OW >= (1LL << 31))
+    throw std::runtime_error("stem conv: inconsistent shapes");
+}
+
+// the stem forwards: fwd_kernel<128, 64> with loader LD over the GEMM view p.run
+template <class XT, class LD>
+static void stem_fwd(const ConvPlan& p, const ConvShape& si, const XT* x, const void* wt, void* yb,
+                     hipStream_t st, const ConvStats* stats, const char* mismatch) {
+  using namespace cbf;
+  const ConvShape& s1 = p.run;
+  ConvStats cs;
+  if (stats && stats->part) {
+    if (stats->P != p.stats_rows)
+      throw std::runtime_error(mismatch);
+    cs = *stats;
+  }
+  const dim3 grid(cdiv((long long)s1.N * s1.OH * s1.OW, p.bm) * (s1.K / p.bn), 1);
+  fwd_kernel<128, 64, XT, LD><<<grid, NT, 0, st>>>(
+      s1, x, reinterpret_cast<const __bf16*>(wt), nullptr, nullptr, 0, p.per, nullptr,
+      reinterpret_cast<__bf16*>(yb), 0, si, cs);
+}
+
+void conv_fwd_stem_bf16(const ConvShape& s1, const ConvShape& si, const float* x, const void* wtb,
+                        void* yb, hipStream_t st, const ConvStats* stats) {
+  stem_check(s1, si);
+  stem_fwd<float, cbf::StemLoader<128, 64>>(plan_fwd_bf16(s1, ConvHave(), 1), si, x, wtb, yb, st,
+                                            stats, "stem conv: BatchNorm statistics layout mismatch");
+}
+
+void conv_bwd_filter_stem_bf16(const ConvShape& s1, const ConvShape& si, const float* x,
+                               const void* dyb, float* ws, float* dw, hipStream_t st) {
+  using namespace cbf;
+  stem_check(s1, si);
+  const ConvPlan p = plan_wgrad_bf16(s1, ConvHave(), 1);
+  if (p.ws_floats && !ws) throw std::runtime_error("stem wgrad: split-K needs a workspace");
+  float* out = p.z > 1 ? ws : dw;
+  const int blocks = cdiv((long long)s1.C, p.bm) * (s1.K / p.bn) * p.z;
+  const __bf16* d = reinterpret_cast<const __bf16*>(dyb);
+#define WG_STEM(BM_, BN_)                                                                  \
+  wgrad_kernel<BM_, BN_, true, StemWgLoader<BM_, BN_>><<<blocks, NT, 0, st>>>(s1, x, d, out, \
+                                                                             p.per, si)
+  TILE_DISPATCH(p, WG_STEM);
+#undef WG_STEM
+  if (p.z > 1) slab_reduce(ws, p.z, (long long)s1.C * s1.K / 4, dw, st);
+}
 
 void conv_fwd_s2d_stem_bf16(const ConvShape& si, const void* xs, const void* wt8, void* yb,
                             hipStream_t st, const ConvStats* stats) {
   using namespace cbf;
-  s2d_check(si);
-  const ConvShape s1 = s2d_gemm_shape(si);
-  ConvStats cs;
-  if (stats && stats->part) {
-    if (stats->P != conv_fwd_stem_stats_rows(s1))
-      throw std::runtime_error("s2d stem conv: BatchNorm statistics layout mismatch");
-    cs = *stats;
-  }
-  const long long M = (long long)s1.N * s1.OH * s1.OW;
-  const dim3 grid(cdiv(M, 128) * (s1.K / 64), 1);
-  if (s1.C / BK != S2dLoaderPre<128, 64>::NKT) throw std::runtime_error("s2d stem conv: K tiles");
-  if (g_s2d_preload)
-    fwd_kernel<128, 64, __bf16, S2dLoaderPre<128, 64>><<<grid, NT, 0, st>>>(
-        s1, reinterpret_cast<const __bf16*>(xs), reinterpret_cast<const __bf16*>(wt8), nullptr,
-        nullptr, 0, s1.C / BK, nullptr, reinterpret_cast<__bf16*>(yb), 0, si, cs);
+  const ConvPlan p = plan_fwd_bf16(si, ConvHave(), 2);
+  if (p.per != S2dLoaderPre<128, 64>::NKT) throw std::runtime_error("s2d stem conv: K tiles");
+  const __bf16* x = reinterpret_cast<const __bf16*>(xs);
+  const char* mismatch = "s2d stem conv: BatchNorm statistics layout mismatch";
+  if (p.kernel == ConvKernel::B16_S2D_FWD_PRE)
+    stem_fwd<__bf16, S2dLoaderPre<128, 64>>(p, si, x, wt8, yb, st, stats, mismatch);
   else
-    fwd_kernel<128, 64, __bf16, S2dLoader<128, 64>><<<grid, NT, 0, st>>>(
-        s1, reinterpret_cast<const __bf16*>(xs), reinterpret_cast<const __bf16*>(wt8), nullptr,
-        nullptr, 0, s1.C / BK, nullptr, reinterpret_cast<__bf16*>(yb), 0, si, cs);
+    stem_fwd<__bf16, S2dLoader<128, 64>>(p, si, x, wt8, yb, st, stats, mismatch);
 }
-void s2d_stem_set_preload(bool on) { g_s2d_preload = on; }
 
 // the 4x4 conv's filter gradient over the s2d image: the generic bf16 wgrad
 // (rows m = tap * 16 + channel; a channel quad never straddles taps), split-K
@@ -2628,96 +2617,9 @@ void conv_bwd_filter_s2d_stem_bf16(const ConvShape& si, const void* xs, const vo
                                    float* ws, float* dw8, hipStream_t st) {
   using namespace cbf;
   s2d_check(si);
-  const WgPlan p = wg_plan(si);
-  if (p.z > 1 && !ws) throw std::runtime_error("s2d stem wgrad: split-K needs a workspace");
-  float* out = p.z > 1 ? ws : dw8;
-  const int blocks = cdiv(256, p.bm) * (si.K / p.bn) * p.z;
-  const __bf16* xh = reinterpret_cast<const __bf16*>(xs);
-  const __bf16* dh = reinterpret_cast<const __bf16*>(dyb);
-  if (p.bm == 128) {
-    if (p.bn == 128)
-      wgrad_kernel<128, 128, true><<<blocks, NT, 0, st>>>(si, xh, dh, out, p.kchunk, si);
-    else
-      wgrad_kernel<128, 64, true><<<blocks, NT, 0, st>>>(si, xh, dh, out, p.kchunk, si);
-  } else if (p.bn == 128) {
-    wgrad_kernel<64, 128, true><<<blocks, NT, 0, st>>>(si, xh, dh, out, p.kchunk, si);
-  } else {
-    wgrad_kernel<64, 64, true><<<blocks, NT, 0, st>>>(si, xh, dh, out, p.kchunk, si);
-  }
-  if (p.z > 1) slab_reduce(ws, p.z, 256LL * si.K / 4, dw8, st);
-}
-
-// The kernel, tile and split the launchers of this file take for s (follows
-// conv_fwd_bf16 / conv_bwd_data_bf16 / conv_bwd_filter_bf16 with the bf16
-// operand copies present, and the stem launchers), from their own plans.
-ConvRoute conv_route_bf16(const ConvShape& s, int op, bool epilogue, int stem) {
-  using namespace cbf;
-  ConvRoute r;
-  r.family = "bf16";
-  auto gemm = [&](const ConvShape& c, bool epi, const char* name) {
-    const Plan p = plan(c, epi);
-    r.kernel = name, r.bm = tm(p.t), r.bn = tn(p.t), r.z = p.z;
-  };
-  auto halo3 = [&](const ConvShape& c) {
-    const P3 p = plan3(c);
-    r.kernel = "conv3_kernel", r.bm = p.bm, r.bn = 64, r.z = p.z, r.halo = true;
-  };
-  auto wg = [&](const ConvShape& c) {
-    const WgPlan p = wg_plan(c);
-    r.kernel = "wgrad_kernel", r.bm = p.bm, r.bn = p.bn, r.z = p.z;
-  };
-  if (stem) {
-    r.stem = true;
-    if (op == 0) {
-      if (stem == 2) s2d_check(s);
-      r.kernel = stem == 2 ? (g_s2d_preload ? "fwd_kernel/S2dLoaderPre" : "fwd_kernel/S2dLoader")
-                           : "fwd_kernel/StemLoader";
-      r.bm = 128, r.bn = 64;
-    } else if (op == 2) {
-      wg(s);
-      if (stem == 1) r.kernel = "wgrad_kernel/StemWgLoader";
-    } else {
-      throw std::runtime_error("conv_route: the stem has no backward-data");
-    }
-    return r;
-  }
-  if (op == 0) {
-    if (!conv_fwd_bf16_ok(s)) throw std::runtime_error("conv_route: not a bf16-family forward");
-    if (!epilogue && conv3_ok(s))
-      halo3(s);
-    else
-      gemm(s, epilogue, "fwd_kernel");
-  } else if (op == 1) {
-    if (!conv_bwd_data_bf16_ok(s)) throw std::runtime_error("conv_route: not a bf16-family dgrad");
-    if (dgrad3s2_ok(s)) {
-      r.kernel = "dgrad3s2_kernel", r.bm = 64, r.bn = 64, r.z = plan3s2(s).z, r.halo = true;
-    } else if (dgrad_1x1s2(s)) {
-      ConvShape d = dgrad_shape(s);
-      d.H = d.OH = s.OH;
-      d.W = d.OW = s.OW;
-      gemm(d, true, "fwd_kernel/ex2");
-    } else if (conv3_ok(dgrad_shape(s))) {
-      halo3(dgrad_shape(s));
-    } else {
-      gemm(dgrad_shape(s), false, "fwd_kernel");
-    }
-  } else {
-    if (!conv_bwd_filter_bf16_ok(s)) throw std::runtime_error("conv_route: not a bf16-family wgrad");
-    if (wgrad3_ok(s)) {
-      r.kernel = "wgrad3_kernel", r.bm = w3::chunk_pixels(s), r.bn = 64, r.z = wgrad3_splits(s);
-      r.halo = true;
-    } else {
-      wg(s);
-    }
-  }
-  return r;
-}
-
-size_t s2d_stem_ws_floats(const ConvShape& si) {
-  using namespace cbf;
-  s2d_check(si);
-  const WgPlan p = wg_plan(si);
-  return p.z > 1 ? (size_t)p.z * 256 * si.K : 0;
+  const ConvPlan p = plan_wgrad_bf16(si, ConvHave(), 2);
+  if (p.ws_floats && !ws) throw std::runtime_error("s2d stem wgrad: split-K needs a workspace");
+  conv_bwd_filter_bf16(p, nullptr, nullptr, ws, dw8, st, xs, dyb);
 }
 
 }  // namespace gops

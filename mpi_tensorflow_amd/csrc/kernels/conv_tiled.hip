@@ -1367,19 +1367,25 @@ static inline Tile pick(long long M, int N, bool bf16, bool narrow = false) {
   return bm ? T128x64 : T64x64;
 }
 
-#define TILED_DISPATCH_P(P, t, KERNEL, GRID, ...)                                        \
-  switch (t) {                                                                            \
-    case T128x128: KERNEL<128, 128, P><<<GRID(128, 128), NT, 0, st>>>(__VA_ARGS__); break; \
-    case T128x64: KERNEL<128, 64, P><<<GRID(128, 64), NT, 0, st>>>(__VA_ARGS__); break;    \
-    case T64x128: KERNEL<64, 128, P><<<GRID(64, 128), NT, 0, st>>>(__VA_ARGS__); break;    \
-    default: KERNEL<64, 64, P><<<GRID(64, 64), NT, 0, st>>>(__VA_ARGS__); break;           \
-  }
-#define TILED_DISPATCH(t, KERNEL, GRID, ...)                  \
-  if (bf16) {                                                 \
-    TILED_DISPATCH_P(BF16, t, KERNEL, GRID, __VA_ARGS__)      \
-  } else {                                                    \
-    TILED_DISPATCH_P(F32, t, KERNEL, GRID, __VA_ARGS__)       \
-  }
+// a kernel instantiated on the four tiles, launched on the plan's
+#define TILED_DISPATCH_P(P, p, KERNEL, GRID, ...)                                              \
+  do {                                                                                         \
+    if (p.bm == 128 && p.bn == 128)                                                            \
+      KERNEL<128, 128, P><<<GRID(128, 128), NT, 0, st>>>(__VA_ARGS__);                         \
+    else if (p.bm == 128)                                                                      \
+      KERNEL<128, 64, P><<<GRID(128, 64), NT, 0, st>>>(__VA_ARGS__);                           \
+    else if (p.bn == 128)                                                                      \
+      KERNEL<64, 128, P><<<GRID(64, 128), NT, 0, st>>>(__VA_ARGS__);                           \
+    else                                                                                       \
+      KERNEL<64, 64, P><<<GRID(64, 64), NT, 0, st>>>(__VA_ARGS__);                             \
+  } while (0)
+#define TILED_DISPATCH(p, KERNEL, GRID, ...)                 \
+  do {                                                       \
+    if (bf16)                                                \
+      TILED_DISPATCH_P(BF16, p, KERNEL, GRID, __VA_ARGS__);  \
+    else                                                     \
+      TILED_DISPATCH_P(F32, p, KERNEL, GRID, __VA_ARGS__);   \
+  } while (0)
 
 }  // namespace tiled
 
@@ -1418,26 +1424,40 @@ static inline int ksplit(long long blocks, int nk) {
   const int kps = cdiv(nk, z);
   return cdiv(nk, kps);
 }
-static inline void fwd_plan(const ConvShape& s, bool epilogue, bool bf16, Tile& t, int& z,
-                            int& kps) {
-  const long long M = (long long)s.N * s.OH * s.OW;
-  t = pick(M, s.K, bf16, s.R == 1 && s.S == 1 && s.stride == 2);
-  const int nk = s.C % BK == 0 ? s.R * s.S * (s.C / BK) : cdiv(s.R * s.S * s.C, BK);
-  z = epilogue ? 1 : ksplit((long long)cdiv(M, tile_m(t)) * cdiv(s.K, tile_n(t)), nk);
-  kps = cdiv(nk, z);
-}
-static inline void data_plan(const ConvShape& s, bool bf16, Tile& t, int& z, int& kps) {
-  const int sd = s.stride;
-  const long long Mph = (long long)s.N * ((s.H + sd - 1) / sd) * ((s.W + sd - 1) / sd);
-  t = pick(Mph * sd * sd, s.C, bf16, sd == 2);
-  const int ntap = cdiv(s.R, sd) * cdiv(s.S, sd);  // taps of the richest phase
-  const int nk = ntap * (s.K / BK);
-  z = ksplit((long long)cdiv(Mph, tile_m(t)) * cdiv(s.C, tile_n(t)) * sd * sd, nk);
-  kps = cdiv(nk, z);
-}
 static inline long long slab_grid(long long n) {
   const long long b = (n / 4 + 255) / 256;
   return b > 4096 ? 4096 : b;
+}
+static inline ConvPlan new_plan(ConvKernel k, const ConvShape& run, Tile t) {
+  ConvPlan p;
+  p.kernel = k, p.run = run, p.bm = tile_m(t), p.bn = tile_n(t), p.bk = BK;
+  return p;
+}
+// split-K slabs of `out` floats each
+static inline void split(ConvPlan& p, int z, int per, long long out) {
+  p.z = z, p.per = per, p.ws_floats = z > 1 ? z * out : 0;
+}
+// fwd_kernel (gather loader for thin inputs); the statistics rows are those
+// of its epilogue, or of the slab reduction
+static inline ConvPlan fwd_plan(const ConvShape& s, bool epilogue, bool bf16) {
+  const long long M = (long long)s.N * s.OH * s.OW;
+  ConvPlan p = new_plan(s.C % BK != 0 ? ConvKernel::T_FWD_GATHER : ConvKernel::T_FWD, s,
+                        pick(M, s.K, bf16, s.R == 1 && s.S == 1 && s.stride == 2));
+  const int nk = s.C % BK == 0 ? s.R * s.S * (s.C / BK) : cdiv(s.R * s.S * s.C, BK);
+  const int z = epilogue ? 1 : ksplit((long long)cdiv(M, p.bm) * cdiv(s.K, p.bn), nk);
+  split(p, z, cdiv(nk, z), M * s.K);
+  if (!epilogue) p.stats_rows = z > 1 ? (int)slab_grid(M * s.K) : cdiv(M, p.bm) * 2;
+  return p;
+}
+static inline ConvPlan data_plan(const ConvShape& s, bool bf16) {
+  const int sd = s.stride;
+  const long long Mph = (long long)s.N * ((s.H + sd - 1) / sd) * ((s.W + sd - 1) / sd);
+  ConvPlan p = new_plan(ConvKernel::T_DATA, s, pick(Mph * sd * sd, s.C, bf16, sd == 2));
+  const int ntap = cdiv(s.R, sd) * cdiv(s.S, sd);  // taps of the richest phase
+  const int nk = ntap * (s.K / BK);
+  const int z = ksplit((long long)cdiv(Mph, p.bm) * cdiv(s.C, p.bn) * sd * sd, nk);
+  split(p, z, cdiv(nk, z), (long long)s.N * s.H * s.W * s.C);
+  return p;
 }
 static inline void slab_sum(const float* part, int z, long long n, float* out, hipStream_t st,
                             const float* addend = nullptr) {
@@ -1463,19 +1483,17 @@ static bool dgrad_fwd_ok(const ConvShape& s) {
 static ConvShape dgrad_fwd_shape(const ConvShape& s) {
   return ConvShape{s.N, s.OH, s.OW, s.K, s.C, s.R, s.S, 1, s.R - 1 - s.pad, s.H, s.W};
 }
-static long long dgrad_fwd_ws_floats(const ConvShape& s) {
-  const long long wf = ((long long)s.R * s.S * s.C * s.K + 3) / 4 * 4;
-  return wf + conv_fwd_tiled_ws_floats(dgrad_fwd_shape(s), false);
+static long long wflip_floats(const ConvShape& s) {
+  return ((long long)s.R * s.S * s.C * s.K + 3) / 4 * 4;
 }
 
 // fp32 3x3 stride-1 halo conv (conv3f_kernel): block rows, channel-chunk split
-// TiledPlan halo_f32_wide: 128-column tiles on 16-channel chunks where K allows
-struct C3fPlan {
-  int bm, bn, ch, z, cps;
-  bool small;  // 64 x 64 on 16-channel chunks with a 288-row halo and a 3-deep ring
-};
+// (bk = the channels of a chunk).  wt: [9][K][C] read at tap 8 - t - the
+// forward passes the stride-1 dgrad copy (wflip layout), the dgrad the HWIO
+// weights.  TiledPlan halo_f32_wide: 128-column tiles on 16-channel chunks
+// where K allows
 constexpr int C3F_SMALL_ROWS = 288;
-static bool conv3f_plan(const ConvShape& s, C3fPlan& p) {
+static bool conv3f_plan(const ConvShape& s, ConvPlan& p) {
   using namespace tiled;
   if (!tiled_plan().halo_f32) return false;
   if (!(s.R == 3 && s.S == 3 && s.stride == 1 && s.pad == 1 && s.OH == s.H && s.OW == s.W))
@@ -1484,9 +1502,11 @@ static bool conv3f_plan(const ConvShape& s, C3fPlan& p) {
     return false;
   const long long M = (long long)s.N * s.H * s.W;
   const bool wide = tiled_plan().halo_f32_wide && s.K % 128 == 0;
+  p = ConvPlan();
+  p.kernel = ConvKernel::T_CONV3F, p.run = s, p.halo = true;
   p.bn = wide ? 128 : 64;
-  p.ch = wide || tiled_plan().halo_f32_ch == 16 ? 16 : 32;
-  const int nch = s.C / p.ch;
+  p.bk = wide || tiled_plan().halo_f32_ch == 16 ? 16 : 32;
+  const int nch = s.C / p.bk;
   // blocks launched with bm-row tiles (channel-chunk split-K below 512 tiles)
   auto grid = [&](int bm, int& z, int& cps) {
     const long long blocks = cdiv(M, bm) * (s.K / p.bn);
@@ -1508,61 +1528,20 @@ static bool conv3f_plan(const ConvShape& s, C3fPlan& p) {
   p.bm = want == 128 || (want == 0 && b128 >= b64 && (z64 > 1 || z128 == 1)) ? 128 : 64;
   if (h3f::halo_rows(s, p.bm) > h3f::HCAP) p.bm = 64;
   if (h3f::halo_rows(s, p.bm) > h3f::HCAP) return false;
-  p.z = p.bm == 128 ? z128 : z64;
-  p.cps = p.bm == 128 ? c128 : c64;
+  split(p, p.bm == 128 ? z128 : z64, p.bm == 128 ? c128 : c64, M * s.K);
   // TiledPlan halo_f32_small: 30.5 KiB of LDS, five blocks a CU instead of four
-  p.small = tiled_plan().halo_f32_small && p.bm == 64 && p.bn == 64 && p.ch == 16 &&
+  p.small = tiled_plan().halo_f32_small && p.bm == 64 && p.bn == 64 && p.bk == 16 &&
             h3f::halo_rows(s, 64) <= C3F_SMALL_ROWS;
   return true;
 }
 bool conv3f_ok(const ConvShape& s) {
-  C3fPlan p;
+  ConvPlan p;
   return conv3f_plan(s, p);
-}
-long long conv3f_ws_floats(const ConvShape& s) {
-  C3fPlan p;
-  if (!conv3f_plan(s, p) || p.z == 1) return 0;
-  return (long long)p.z * s.N * s.H * s.W * s.K;
-}
-// wt: [9][K][C] read at tap 8 - t (see conv3f_kernel)
-void conv3f(const ConvShape& s, const float* x, const float* wt, float* y, float* ws,
-            hipStream_t st, const float* addend) {
-  using namespace tiled;
-  C3fPlan p;
-  if (!conv3f_plan(s, p)) throw std::runtime_error("conv3f: unsupported shape");
-  if (p.z > 1 && !ws) throw std::runtime_error("conv3f: split-K needs a workspace");
-  const long long M = (long long)s.N * s.H * s.W;
-  float* out = p.z > 1 ? ws : y;
-  const float* add = p.z > 1 ? nullptr : addend;
-  const dim3 grid(cdiv(M, p.bm) * (s.K / p.bn), p.z);
-#define C3F(BM_, BN_, CH_) conv3f_kernel<BM_, BN_, 4, CH_><<<grid, NT, 0, st>>>(s, x, wt, out, p.cps, add)
-  if (p.bn == 128) {
-    if (p.bm == 128)
-      C3F(128, 128, 16);
-    else
-      C3F(64, 128, 16);
-  } else if (p.small) {
-    conv3f_kernel<64, 64, 3, 16, C3F_SMALL_ROWS><<<grid, NT, 0, st>>>(s, x, wt, out, p.cps, add);
-  } else if (p.ch == 16) {  // 64-byte rows: 38 KiB of LDS, four blocks a CU
-    if (p.bm == 128)
-      C3F(128, 64, 16);
-    else
-      C3F(64, 64, 16);
-  } else if (p.bm == 128) {
-    C3F(128, 64, 32);
-  } else {
-    C3F(64, 64, 32);
-  }
-#undef C3F
-  if (p.z > 1) slab_sum(ws, p.z, M * s.K, y, st, addend);
 }
 
 // fp32 3x3 stride-2 dgrad on the halo kernel (dgrad3s2f_kernel): 64 x 64 tiles
 // on 16-channel chunks (38 KiB of LDS), channel-chunk split-K below 512 tiles
-struct D3s2fPlan {
-  int z, cps;
-};
-static bool dgrad3s2f_plan(const ConvShape& s, D3s2fPlan& p) {
+static bool dgrad3s2f_plan(const ConvShape& s, ConvPlan& p) {
   using namespace tiled;
   if (!tiled_plan().halo_f32_s2) return false;
   if (!(s.R == 3 && s.S == 3 && s.stride == 2 && s.pad == 1 && s.H == 2 * s.OH && s.W == 2 * s.OW))
@@ -1573,151 +1552,39 @@ static bool dgrad3s2f_plan(const ConvShape& s, D3s2fPlan& p) {
   const long long blocks = cdiv((long long)s.N * s.OH * s.OW, 64) * (s.C / 64);
   const int nch = s.K / 16;
   const int target = tiled_plan().ksplit_s2 > 0 ? tiled_plan().ksplit_s2 : ksplit_target();
-  p.z = 1;
-  if (blocks < 512) p.z = (int)std::min<long long>(nch, cdiv(target, blocks));
-  p.cps = cdiv(nch, p.z);
-  p.z = cdiv(nch, p.cps);
+  int z = 1;
+  if (blocks < 512) z = (int)std::min<long long>(nch, cdiv(target, blocks));
+  const int cps = cdiv(nch, z);
+  p = new_plan(ConvKernel::T_DGRAD3S2F, s, T64x64);
+  p.bk = 16, p.halo = true;
+  split(p, cdiv(nch, cps), cps, (long long)s.N * s.H * s.W * s.C);
   return true;
 }
-static long long dgrad3s2f_ws_floats(const ConvShape& s) {
-  D3s2fPlan p;
-  if (!dgrad3s2f_plan(s, p) || p.z == 1) return 0;
-  return (long long)p.z * s.N * s.H * s.W * s.C;
+
+// ------------------------------------------------------------ planners ----
+// The caller (plan_fwd / plan_dgrad / plan_wgrad, ops_generic.hip) has checked
+// the *_tiled_ok predicate of the op.
+ConvPlan plan_fwd_tiled(const ConvShape& s, bool bf16, const ConvHave& h) {
+  ConvPlan p;
+  // fp32 with the stride-1 dgrad weight copy: the 3x3 stride-1 layers on the
+  // halo kernel, which has no epilogue and writes no statistics
+  if (!bf16 && h.wcopy && !h.epilogue && !h.stats && conv3f_plan(s, p)) return p;
+  return tiled::fwd_plan(s, h.epilogue, bf16);
 }
 
-// workspace for either operand precision (the plans differ in tile shape)
-long long conv_fwd_tiled_ws_floats(const ConvShape& s, bool epilogue) {
-  long long n = conv3f_ws_floats(s);
-  for (const bool b : {false, true}) {
-    tiled::Tile t;
-    int z, kps;
-    tiled::fwd_plan(s, epilogue, b, t, z, kps);
-    if (z > 1) n = std::max(n, (long long)z * s.N * s.OH * s.OW * s.K);
-  }
-  return n;
-}
-
-long long conv_bwd_data_tiled_ws_floats(const ConvShape& s) {
-  long long n = dgrad_fwd_ok(s) ? dgrad_fwd_ws_floats(s) : 0;
-  n = std::max(n, dgrad3s2f_ws_floats(s));
-  if (dgrad_fwd_ok(s)) n = std::max(n, conv3f_ws_floats(dgrad_fwd_shape(s)));
-  for (const bool b : {false, true}) {
-    tiled::Tile t;
-    int z, kps;
-    tiled::data_plan(s, b, t, z, kps);
-    if (z > 1) n = std::max(n, (long long)z * s.N * s.H * s.W * s.C);
-  }
-  return n;
-}
-
-int conv_fwd_tiled_stats_rows(const ConvShape& s, bool bf16) {
-  using namespace tiled;
-  const long long M = (long long)s.N * s.OH * s.OW;
-  Tile t;
-  int z, kps;
-  fwd_plan(s, false, bf16, t, z, kps);
-  return z > 1 ? (int)slab_grid(M * s.K) : cdiv(M, tile_m(t)) * 2;
-}
-
-static void conv_fwd_tiled_impl(const ConvShape& s, const float* x, const float* w,
-                                const float* bias, float* y, bool relu, float* ws,
-                                hipStream_t st, bool bf16, const ConvStats* stats,
-                                const float* addend);
-
-void conv_fwd_tiled(const ConvShape& s, const float* x, const float* w, const float* bias, float* y,
-                    bool relu, float* ws, hipStream_t st, bool bf16, const ConvStats* stats) {
-  conv_fwd_tiled_impl(s, x, w, bias, y, relu, ws, st, bf16, stats, nullptr);
-}
-
-static void conv_fwd_tiled_impl(const ConvShape& s, const float* x, const float* w,
-                                const float* bias, float* y, bool relu, float* ws,
-                                hipStream_t st, bool bf16, const ConvStats* stats,
-                                const float* addend) {
-  using namespace tiled;
-  const long long M = (long long)s.N * s.OH * s.OW;
-  Tile t;
-  int z, kps;
-  fwd_plan(s, bias != nullptr || relu, bf16, t, z, kps);
-  if (z > 1 && !ws) throw std::runtime_error("conv_fwd_tiled: split-K needs a workspace");
-  ConvStats cs;
-  if (stats && stats->part) {
-    if (bias || relu || s.K % 64 || 256 % (s.K / 4) ||
-        stats->P != conv_fwd_tiled_stats_rows(s, bf16))
-      throw std::runtime_error("conv_fwd_tiled: BatchNorm statistics layout mismatch");
-    if (z == 1) cs = *stats;
-  }
-  float* out = z > 1 ? ws : y;
-#define GRID(BM_, BN_) dim3(cdiv(M, BM_) * cdiv(s.K, BN_), z)
-  if (s.C % BK != 0) {  // gather loader (fp32 operands only)
-    if (bf16) throw std::runtime_error("conv_fwd_tiled: the gather forward is fp32");
-#define F32G F32, true
-    TILED_DISPATCH_P(F32G, t, fwd_kernel, GRID, s, x, w, bias, out, relu ? 1 : 0, kps, cs,
-                     z > 1 ? nullptr : addend)
-#undef F32G
-  } else {
-    TILED_DISPATCH(t, fwd_kernel, GRID, s, x, w, bias, out, relu ? 1 : 0, kps, cs,
-                   z > 1 ? nullptr : addend)
-  }
-#undef GRID
-  if (z > 1) {
-    if (addend && stats && stats->part)
-      throw std::runtime_error("conv_fwd_tiled: statistics with an addend");
-    if (stats && stats->part)
-      slab_sum4_stats_kernel<<<(int)slab_grid(M * s.K), 256, 0, st>>>(
-          reinterpret_cast<const float4*>(ws), z, M * s.K / 4, reinterpret_cast<float4*>(y),
-          *stats, s.K);
-    else
-      slab_sum(ws, z, M * s.K, y, st, addend);
-  }
-}
-
-void conv_bwd_data_tiled(const ConvShape& s, const float* dy, const float* w, float* dx, float* ws,
-                         hipStream_t st, bool bf16, const float* addend, const void* dyb,
-                         const float* wflip) {
-  using namespace tiled;
-  if (!bf16 && dy && ws && dgrad_fwd_ok(s)) {
+ConvPlan plan_dgrad_tiled(const ConvShape& s, bool bf16, const ConvHave& h) {
+  ConvPlan p;
+  if (!bf16 && h.dy32 && h.ws && dgrad_fwd_ok(s)) {
     const ConvShape f = dgrad_fwd_shape(s);
-    if (conv3f_ok(f)) {  // the halo kernel reads W itself, taps reversed (conv3f_kernel)
-      conv3f(f, dy, w, dx, ws, st, addend);
-      return;
-    }
-    float* fws = ws + ((long long)s.R * s.S * s.C * s.K + 3) / 4 * 4;
-    const float* wt = wflip;  // kept current by the step's SGD (gops::sgd_wcvt)
-    if (!wt) {
-      wflip_kernel<<<dim3(cdiv(s.K, 32), cdiv(s.C, 32), s.R * s.S), 256, 0, st>>>(w, ws, s.R, s.S,
-                                                                                 s.C, s.K);
-      wt = ws;
-    }
-    conv_fwd_tiled_impl(f, dy, wt, nullptr, dx, false, fws, st, false, nullptr, addend);
-    return;
+    if (conv3f_plan(f, p)) return p;  // the halo kernel reads W itself, taps reversed
+    p = tiled::fwd_plan(f, false, false);
+    p.slabs = wflip_floats(s), p.ws_floats += p.slabs, p.stats_rows = 0;
+    return p;
   }
-  D3s2fPlan dp;
-  if (!bf16 && dy && dgrad3s2f_plan(s, dp)) {
-    if (dp.z > 1 && !ws) throw std::runtime_error("dgrad3s2f: split-K needs a workspace");
-    const dim3 grid(cdiv((long long)s.N * s.OH * s.OW, 64) * (s.C / 64), dp.z);
-    dgrad3s2f_kernel<64, 64, 4, 16><<<grid, NT, 0, st>>>(s, dy, w, dp.z > 1 ? ws : dx, dp.cps,
-                                                         dp.z > 1 ? nullptr : addend);
-    if (dp.z > 1) slab_sum(ws, dp.z, (long long)s.N * s.H * s.W * s.C, dx, st, addend);
-    return;
-  }
-  const int sd = s.stride;
-  const long long Mph = (long long)s.N * ((s.H + sd - 1) / sd) * ((s.W + sd - 1) / sd);
-  Tile t;
-  int z, kps;
-  data_plan(s, bf16, t, z, kps);
-  if (z > 1 && !ws) throw std::runtime_error("conv_bwd_data_tiled: split-K needs a workspace");
-  float* out = z > 1 ? ws : dx;
-  // phases no tap reaches (odd pixels of a 1x1 stride-2 conv) run zero K
-  // tiles and write zeros
-#define GRID(BM_, BN_) dim3(cdiv(Mph, BM_) * cdiv(s.C, BN_), sd * sd, z)
-  if (!dy && dyb) {  // dY only as bf16: bf16 loads, converted in registers
-    const __bf16* d16 = reinterpret_cast<const __bf16*>(dyb);
-    TILED_DISPATCH(t, data_b16_kernel, GRID, s, d16, w, out, kps, z > 1 ? nullptr : addend)
-  } else {
-    TILED_DISPATCH(t, data_kernel, GRID, s, dy, w, out, kps, z > 1 ? nullptr : addend)
-  }
-#undef GRID
-  if (z > 1) slab_sum(ws, z, (long long)s.N * s.H * s.W * s.C, dx, st, addend);
+  if (!bf16 && h.dy32 && dgrad3s2f_plan(s, p)) return p;
+  p = tiled::data_plan(s, bf16);
+  if (!h.dy32 && h.act16) p.kernel = ConvKernel::T_DATA_B16;  // bf16 loads, converted in registers
+  return p;
 }
 
 namespace tiled {
@@ -1729,21 +1596,14 @@ static inline Tile filter_tile(const ConvShape& s) {  // ci x co tiles
   const bool bm = s.C >= 128 && !tiled_plan().wg64, bn = s.K > 64 && !tiled_plan().wg_n64;
   return bm ? (bn ? T128x128 : T128x64) : (bn ? T64x128 : T64x64);
 }
-static inline int filter_blocks_per_split(const ConvShape& s) {
-  const Tile t = filter_tile(s);
-  const int BM = (t == T128x128 || t == T128x64) ? 128 : 64;
-  const int BN = (t == T128x128 || t == T64x128) ? 128 : 64;
-  return cdiv(s.C, BM) * cdiv(s.K, BN) * s.R * s.S;
-}
-}  // namespace tiled
-
-namespace tiled {
 // slices launched (padded to a multiple of 8 for the XCD order) and the K
 // tiles of each
 static int filter_splits(const ConvShape& s, int& kchunk) {
   const int ktiles = cdiv((long long)s.N * s.OH * s.OW, BK);
   const bool vec = s.C % 4 == 0;
-  const int tiles = vec ? filter_blocks_per_split(s) : cdiv(s.R * s.S * s.C, 64) * cdiv(s.K, 64);
+  const Tile t = filter_tile(s);
+  const int tiles = vec ? cdiv(s.C, tile_m(t)) * cdiv(s.K, tile_n(t)) * s.R * s.S
+                        : cdiv(s.R * s.S * s.C, 64) * cdiv(s.K, 64);
   // blocks to aim for (TiledPlan wgsplit_target).  With the walked pixel
   // coordinates (PixWalk) fewer, longer slices pay: ResNet-18 fp32 filter
   // gradients in conv_lab 1934 / 1805 / 1836 / 1901 us a step at 2048 / 1024 /
@@ -1772,97 +1632,188 @@ static int filter_splits(const ConvShape& s, int& kchunk) {
 }
 }  // namespace tiled
 
-int conv_filter_tiled_splits(const ConvShape& s) {
-  int kchunk;
-  return tiled::filter_splits(s, kchunk);
-}
-
-void conv_bwd_filter_tiled(const ConvShape& s, const float* x, const float* dy, float* part,
-                           float* dw, hipStream_t st, bool bf16) {
+ConvPlan plan_wgrad_tiled(const ConvShape& s, bool bf16) {
   using namespace tiled;
+  const bool vec = s.C % 4 == 0;  // else (tap, ci) gather rows, 64 x 64 tiles
+  ConvPlan p = new_plan(vec ? ConvKernel::T_FILTER : ConvKernel::T_FILTER_GATHER, s,
+                        vec ? filter_tile(s) : T64x64);
   int kchunk;
   const int z = filter_splits(s, kchunk);
-  const bool xcd = tiled_plan().wg_xcd;
-  const int taps = s.R * s.S;
-  if (s.C % 4 != 0) {  // (tap, ci) gather rows, 64x64 tiles
-    const int Mw = taps * s.C;
-    if (bf16)
-      filter_gather_kernel<64, 64, BF16><<<cdiv(Mw, 64) * cdiv(s.K, 64) * z, NT, 0, st>>>(
-          s, x, dy, z == 1 ? dw : part, kchunk, xcd);
-    else
-      filter_gather_kernel<64, 64, F32><<<cdiv(Mw, 64) * cdiv(s.K, 64) * z, NT, 0, st>>>(
-          s, x, dy, z == 1 ? dw : part, kchunk, xcd);
-    if (z > 1) slab_sum(part, z, (long long)Mw * s.K, dw, st);
-    return;
-  }
-  const Tile t = filter_tile(s);
-#define GRID(BM_, BN_) dim3(cdiv(s.C, BM_) * cdiv(s.K, BN_) * taps * z)
+  split(p, z, kchunk, (long long)s.R * s.S * s.C * s.K);
   // 16-pixel K tiles (the same slices in twice the tiles): 64 x 128 in 24 KiB of
   // LDS, five blocks a CU instead of three - filter gradients 1806 -> 1773 us a
   // step, ResNet-18 fp32 5.412 / 5.413 -> 5.379 / 5.387 ms (r6_s43.steps)
-  if (!bf16 && t == T64x128 && tiled_plan().wg_bk16) {
-    filter_kernel<64, 128, F32, 16><<<GRID(64, 128), NT, 0, st>>>(s, x, dy, z == 1 ? dw : part,
-                                                                 2 * kchunk, xcd);
-  } else if (!bf16 && t == T64x64 && tiled_plan().wg_bk16_64) {
-    filter_kernel<64, 64, F32, 16><<<GRID(64, 64), NT, 0, st>>>(s, x, dy, z == 1 ? dw : part,
-                                                               2 * kchunk, xcd);
-  } else {
-    TILED_DISPATCH(t, filter_kernel, GRID, s, x, dy, z == 1 ? dw : part, kchunk, xcd)
-  }
-#undef GRID
-  if (z > 1) slab_sum(part, z, (long long)taps * s.C * s.K, dw, st);
+  if (vec && !bf16 && p.bm == 64 && (p.bn == 128 ? tiled_plan().wg_bk16 : tiled_plan().wg_bk16_64))
+    p.bk = 16, p.per = 2 * kchunk;
+  return p;
 }
 
-// The kernel, tile and split this family's launchers take for s (follows
-// conv3f / conv_fwd_tiled / conv_bwd_data_tiled / conv_bwd_filter_tiled), from
-// their own plans.  The caller has checked the *_tiled_ok predicate.
-ConvRoute conv_route_tiled(const ConvShape& s, int op, bool bf16, bool epilogue, bool wcopy) {
+// workspace for either operand precision (the plans differ in tile shape) and
+// with or without the weight copy: the conv mode can change after the
+// workspace is built
+long long conv_fwd_tiled_ws_floats(const ConvShape& s, bool epilogue) {
+  ConvPlan p;
+  long long n = conv3f_plan(s, p) ? p.ws_floats : 0;
+  for (const bool b : {false, true}) n = std::max(n, tiled::fwd_plan(s, epilogue, b).ws_floats);
+  return n;
+}
+
+long long conv_bwd_data_tiled_ws_floats(const ConvShape& s) {
+  ConvPlan p;
+  long long n = 0;
+  if (dgrad_fwd_ok(s)) n = wflip_floats(s) + conv_fwd_tiled_ws_floats(dgrad_fwd_shape(s), false);
+  if (dgrad3s2f_plan(s, p)) n = std::max(n, p.ws_floats);
+  for (const bool b : {false, true}) n = std::max(n, tiled::data_plan(s, b).ws_floats);
+  return n;
+}
+
+// ----------------------------------------------------------- launchers ----
+// conv3f_kernel on p.run (the forward's own shape, or the dgrad's forward shape)
+static void conv3f(const ConvPlan& p, const float* x, const float* wt, float* y, float* ws,
+                   hipStream_t st, const float* addend) {
   using namespace tiled;
-  ConvRoute r;
-  r.family = "tiled";
-  auto halo = [&](const ConvShape& c) {
-    C3fPlan p;
-    conv3f_plan(c, p);
-    r.kernel = "conv3f_kernel", r.bm = p.bm, r.bn = p.bn, r.z = p.z, r.halo = true;
-  };
-  auto fwd = [&](const ConvShape& c, bool epi, bool b16) {
-    Tile t;
-    int z, kps;
-    fwd_plan(c, epi, b16, t, z, kps);
-    r.kernel = c.C % BK != 0 ? "fwd_kernel/gather" : "fwd_kernel";
-    r.bm = tile_m(t), r.bn = tile_n(t), r.z = z;
-  };
-  if (op == 0) {
-    if (!bf16 && wcopy && !epilogue && conv3f_ok(s))
-      halo(s);
+  const ConvShape& s = p.run;
+  const long long M = (long long)s.N * s.H * s.W;
+  float* out = p.z > 1 ? ws : y;
+  const float* add = p.z > 1 ? nullptr : addend;
+  const dim3 grid(cdiv(M, p.bm) * (s.K / p.bn), p.z);
+#define C3F(BM_, BN_, CH_) conv3f_kernel<BM_, BN_, 4, CH_><<<grid, NT, 0, st>>>(s, x, wt, out, p.per, add)
+  if (p.bn == 128) {
+    if (p.bm == 128)
+      C3F(128, 128, 16);
     else
-      fwd(s, epilogue, bf16);
-  } else if (op == 1) {
-    D3s2fPlan dp;
-    if (!bf16 && dgrad_fwd_ok(s)) {
-      if (conv3f_ok(dgrad_fwd_shape(s)))
-        halo(dgrad_fwd_shape(s));
-      else
-        fwd(dgrad_fwd_shape(s), false, false);
-    } else if (!bf16 && dgrad3s2f_plan(s, dp)) {
-      r.kernel = "dgrad3s2f_kernel", r.bm = 64, r.bn = 64, r.z = dp.z, r.halo = true;
-    } else {
-      Tile t;
-      int z, kps;
-      data_plan(s, bf16, t, z, kps);
-      r.kernel = "data_kernel", r.bm = tile_m(t), r.bn = tile_n(t), r.z = z;
-    }
+      C3F(64, 128, 16);
+  } else if (p.small) {
+    conv3f_kernel<64, 64, 3, 16, C3F_SMALL_ROWS><<<grid, NT, 0, st>>>(s, x, wt, out, p.per, add);
+  } else if (p.bk == 16) {  // 64-byte rows: 38 KiB of LDS, four blocks a CU
+    if (p.bm == 128)
+      C3F(128, 64, 16);
+    else
+      C3F(64, 64, 16);
+  } else if (p.bm == 128) {
+    C3F(128, 64, 32);
   } else {
-    int kchunk;
-    r.z = filter_splits(s, kchunk);
-    if (s.C % 4 != 0) {
-      r.kernel = "filter_gather_kernel", r.bm = 64, r.bn = 64;
-    } else {
-      const Tile t = filter_tile(s);
-      r.kernel = "filter_kernel", r.bm = tile_m(t), r.bn = tile_n(t);
+    C3F(64, 64, 32);
+  }
+#undef C3F
+  if (p.z > 1) slab_sum(ws, p.z, M * s.K, y, st, addend);
+}
+
+// fwd_kernel on p.run; ws: the slabs
+static void fwd_gemm(const ConvPlan& p, const float* x, const float* w, const float* bias, float* y,
+                     bool relu, float* ws, hipStream_t st, bool bf16, const ConvStats* stats,
+                     const float* addend) {
+  using namespace tiled;
+  const ConvShape& s = p.run;
+  const long long M = (long long)s.N * s.OH * s.OW;
+  const int z = p.z, kps = p.per;
+  ConvStats cs;
+  if (stats && stats->part && z == 1) cs = *stats;
+  float* out = z > 1 ? ws : y;
+#define GRID(BM_, BN_) dim3(cdiv(M, BM_) * cdiv(s.K, BN_), z)
+  if (p.kernel == ConvKernel::T_FWD_GATHER) {  // fp32 operands only
+#define F32G F32, true
+    TILED_DISPATCH_P(F32G, p, fwd_kernel, GRID, s, x, w, bias, out, relu ? 1 : 0, kps, cs,
+                     z > 1 ? nullptr : addend);
+#undef F32G
+  } else {
+    TILED_DISPATCH(p, fwd_kernel, GRID, s, x, w, bias, out, relu ? 1 : 0, kps, cs,
+                   z > 1 ? nullptr : addend);
+  }
+#undef GRID
+  if (z > 1) {
+    if (stats && stats->part)
+      slab_sum4_stats_kernel<<<(int)slab_grid(M * s.K), 256, 0, st>>>(
+          reinterpret_cast<const float4*>(ws), z, M * s.K / 4, reinterpret_cast<float4*>(y),
+          *stats, s.K);
+    else
+      slab_sum(ws, z, M * s.K, y, st, addend);
+  }
+}
+
+// wt: the fp32 stride-1 dgrad weight copy (T_CONV3F only)
+void conv_fwd_tiled(const ConvPlan& p, const float* x, const float* w, const float* wt,
+                    const float* bias, float* y, bool relu, float* ws, hipStream_t st, bool bf16,
+                    const ConvStats* stats) {
+  if (p.kernel == ConvKernel::T_CONV3F) return conv3f(p, x, wt, y, ws, st, nullptr);
+  if (p.kernel == ConvKernel::T_FWD_GATHER && bf16)
+    throw std::runtime_error("conv_fwd_tiled: the gather forward is fp32");
+  if (stats && stats->part &&
+      (p.stats_rows == 0 || stats->P != p.stats_rows || p.run.K % 64 || 256 % (p.run.K / 4)))
+    throw std::runtime_error("conv_fwd_tiled: BatchNorm statistics layout mismatch");
+  fwd_gemm(p, x, w, bias, y, relu, ws, st, bf16, stats, nullptr);
+}
+
+// dy may be null when dyb (bf16 dY) is given
+// wflip (optional, fp32 stride-1 dgrad): the weights already flipped and
+// ci / co-transposed, W'[kh][kw][co][ci] = W[R-1-kh][S-1-kw][ci][co]
+// (wcvt_batch mode 2 / sgd_wcvt fp32 jobs); else a wflip launch derives them
+void conv_bwd_data_tiled(const ConvPlan& p, const ConvShape& s, const float* dy, const float* w,
+                         float* dx, float* ws, hipStream_t st, bool bf16, const float* addend,
+                         const void* dyb, const float* wflip) {
+  using namespace tiled;
+  const long long n = (long long)s.N * s.H * s.W * s.C;
+  const float* add = p.z > 1 ? nullptr : addend;  // split-K: added by the slab reduction
+  float* out = p.z > 1 ? ws : dx;
+  switch (p.kernel) {
+    case ConvKernel::T_CONV3F: return conv3f(p, dy, w, dx, ws, st, addend);
+    case ConvKernel::T_FWD: {  // the forward kernel over dY
+      const float* wt = wflip;  // kept current by the step's SGD (gops::sgd_wcvt)
+      if (!wt) {
+        wflip_kernel<<<dim3(cdiv(s.K, 32), cdiv(s.C, 32), s.R * s.S), 256, 0, st>>>(w, ws, s.R, s.S,
+                                                                                   s.C, s.K);
+        wt = ws;
+      }
+      return fwd_gemm(p, dy, wt, nullptr, dx, false, ws + p.slabs, st, false, nullptr, addend);
+    }
+    case ConvKernel::T_DGRAD3S2F: {
+      const dim3 grid(cdiv((long long)s.N * s.OH * s.OW, 64) * (s.C / 64), p.z);
+      dgrad3s2f_kernel<64, 64, 4, 16><<<grid, NT, 0, st>>>(s, dy, w, out, p.per, add);
+      break;
+    }
+    default: {
+      const int sd = s.stride;
+      const long long Mph = (long long)s.N * ((s.H + sd - 1) / sd) * ((s.W + sd - 1) / sd);
+      // phases no tap reaches (odd pixels of a 1x1 stride-2 conv) run zero K
+      // tiles and write zeros
+#define GRID(BM_, BN_) dim3(cdiv(Mph, BM_) * cdiv(s.C, BN_), sd * sd, p.z)
+      if (p.kernel == ConvKernel::T_DATA_B16) {
+        const __bf16* d16 = reinterpret_cast<const __bf16*>(dyb);
+        TILED_DISPATCH(p, data_b16_kernel, GRID, s, d16, w, out, p.per, add);
+      } else {
+        TILED_DISPATCH(p, data_kernel, GRID, s, dy, w, out, p.per, add);
+      }
+#undef GRID
     }
   }
-  return r;
+  if (p.z > 1) slab_sum(ws, p.z, n, dx, st, addend);
+}
+
+void conv_bwd_filter_tiled(const ConvPlan& p, const float* x, const float* dy, float* part,
+                           float* dw, hipStream_t st, bool bf16) {
+  using namespace tiled;
+  const ConvShape& s = p.run;
+  const bool xcd = tiled_plan().wg_xcd;
+  const int taps = s.R * s.S, z = p.z;
+  float* out = z == 1 ? dw : part;
+  if (p.kernel == ConvKernel::T_FILTER_GATHER) {
+    const int blocks = cdiv(taps * s.C, 64) * cdiv(s.K, 64) * z;
+    if (bf16)
+      filter_gather_kernel<64, 64, BF16><<<blocks, NT, 0, st>>>(s, x, dy, out, p.per, xcd);
+    else
+      filter_gather_kernel<64, 64, F32><<<blocks, NT, 0, st>>>(s, x, dy, out, p.per, xcd);
+  } else {
+#define GRID(BM_, BN_) dim3(cdiv(s.C, BM_) * cdiv(s.K, BN_) * taps * z)
+    if (p.bk == 16 && p.bn == 128) {
+      filter_kernel<64, 128, F32, 16><<<GRID(64, 128), NT, 0, st>>>(s, x, dy, out, p.per, xcd);
+    } else if (p.bk == 16) {
+      filter_kernel<64, 64, F32, 16><<<GRID(64, 64), NT, 0, st>>>(s, x, dy, out, p.per, xcd);
+    } else {
+      TILED_DISPATCH(p, filter_kernel, GRID, s, x, dy, out, p.per, xcd);
+    }
+#undef GRID
+  }
+  if (z > 1) slab_sum(part, z, (long long)taps * s.C * s.K, dw, st);
 }
 
 }  // namespace gops

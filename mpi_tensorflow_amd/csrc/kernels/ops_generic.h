@@ -49,6 +49,64 @@ struct BnBwdStats {
   const float* rstd = nullptr;
   int relu = 0;
 };
+// The launch decision of one conv call, as a value: the planners below build
+// it, the launchers execute it, conv_route prints it and the size queries
+// read its workspace and statistics fields.
+enum class ConvKernel {
+  // conv_bf16.hip (family "bf16")
+  B16_FWD, B16_FWD_EX2, B16_CONV3, B16_DGRAD3S2, B16_WGRAD, B16_WGRAD3,
+  B16_STEM_FWD, B16_S2D_FWD_PRE, B16_S2D_FWD, B16_STEM_WGRAD,
+  // conv_tiled.hip (family "tiled")
+  T_FWD, T_FWD_GATHER, T_CONV3F, T_DATA, T_DATA_B16, T_DGRAD3S2F, T_FILTER, T_FILTER_GATHER,
+  // ops_generic.hip (families "direct" and "gather")
+  DIRECT_FWD, DIRECT_DGRAD, GATHER_FWD, GATHER_DGRAD, GATHER_WGRAD,
+  COUNT
+};
+// (the families are ranges of the enum; conv_route's name table is held to COUNT)
+inline bool conv_kernel_bf16(ConvKernel k) { return k <= ConvKernel::B16_STEM_WGRAD; }
+inline bool conv_kernel_tiled(ConvKernel k) {
+  return k >= ConvKernel::T_FWD && k <= ConvKernel::T_FILTER_GATHER;
+}
+// What a call provides (the defaults: ops/functional.py in bf16 conv mode,
+// every copy passed, no statistics).
+struct ConvHave {
+  bool epilogue = false;  // a bias / ReLU forward
+  bool act16 = true;      // the bf16 copy of the activation operand: xb (forward, filter
+                          // gradient: with dy16 below), dyb (backward-data)
+  bool dy16 = true;       // filter gradient: the bf16 dY
+  bool dy32 = true;       // backward-data: the fp32 dY
+  bool wcopy = false;     // fp32 forward: the stride-1 dgrad weight copy (wtb)
+  bool ws = true;         // a workspace
+  bool stats = false;     // forward BatchNorm statistics wanted
+};
+struct ConvPlan {
+  ConvKernel kernel = ConvKernel::GATHER_FWD;
+  int bm = 0, bn = 0;     // block tile (rows x columns of the kernel's GEMM)
+  int bk = 0;             // K-tile depth: pixels (filter gradients) or channels a chunk
+  int z = 1;              // split-K slabs
+  int per = 0;            // K tiles / channel chunks / pixel chunks of a slice (kps, cps, kchunk)
+  bool halo = false, stem = false;
+  bool small = false;     // conv3f_kernel: the 288-row halo form (TiledPlan halo_f32_small)
+  bool addend_ok = true;  // the route has a gradient-join epilogue
+  ConvShape run{};        // the shape the kernel runs on
+  long long ws_floats = 0;  // workspace the launch needs ...
+  long long slabs = 0;      // ... and where its split-K slabs start (after a weight copy)
+  int stats_rows = 0;     // BatchNorm statistics rows it writes (0: it cannot)
+};
+// op by op: the family is chosen here, its kernel by the family's planner
+// (conv_tiled.hip, conv_bf16.hip).  stem (plan_fwd / plan_wgrad): 0 = the
+// shape goes through conv_fwd / conv_bwd_filter; 1 = s is the 1x1 GEMM view of
+// conv_fwd_stem_bf16 / conv_bwd_filter_stem_bf16; 2 = s is the 4x4 conv of
+// conv_fwd_s2d_stem_bf16 / conv_bwd_filter_s2d_stem_bf16.
+ConvPlan plan_fwd(const ConvShape& s, bool bf16, const ConvHave& h, int stem = 0);
+ConvPlan plan_dgrad(const ConvShape& s, bool bf16, const ConvHave& h);
+ConvPlan plan_wgrad(const ConvShape& s, bool bf16, const ConvHave& h, int stem = 0);
+ConvPlan plan_fwd_bf16(const ConvShape& s, const ConvHave& h, int stem = 0);
+ConvPlan plan_dgrad_bf16(const ConvShape& s, const ConvHave& h);
+ConvPlan plan_wgrad_bf16(const ConvShape& s, const ConvHave& h, int stem = 0);
+ConvPlan plan_fwd_tiled(const ConvShape& s, bool bf16, const ConvHave& h);
+ConvPlan plan_dgrad_tiled(const ConvShape& s, bool bf16, const ConvHave& h);
+ConvPlan plan_wgrad_tiled(const ConvShape& s, bool bf16);
 int conv_bwd_data_stats_rows(const ConvShape& s);
 // bf16 = true: bf16 family, bf16 output; false: the fp32 tiled forward (no bias / ReLU)
 int conv_fwd_stats_rows(const ConvShape& s, bool bf16 = true);
@@ -68,25 +126,16 @@ void conv_bwd_filter(const ConvShape& s, const float* x, const float* dy, float*
                      hipStream_t st, bool bf16 = false, const void* xb = nullptr,
                      const void* dyb = nullptr);
 long long conv_ws_floats(const ConvShape& s, bool fwd_epilogue);
-// The kernel the launchers above pick for a shape (read-only; tests assert
-// it so that a plan change cannot move a case onto another kernel unseen).
-// op: 0 forward, 1 backward-data, 2 backward-filter.  bf16: bf16 conv mode
-// with the bf16 operand copies present (as ops/functional.py always passes
-// them).  epilogue: a bias / ReLU forward.  wcopy: the fp32 stride-1 dgrad
-// weight copy is passed (fp32 forward only).  stem: 0 = the shape goes through
-// conv_fwd / conv_bwd_data / conv_bwd_filter; 1 = s is the 1x1 GEMM view of
-// conv_fwd_stem_bf16 / conv_bwd_filter_stem_bf16; 2 = s is the 4x4 conv of
-// conv_fwd_s2d_stem_bf16 / conv_bwd_filter_s2d_stem_bf16.
+// The plan the launchers above execute for a call, with the names of its
+// kernel (read-only; tests assert it so that a plan change cannot move a case
+// onto another kernel unseen).  op: 0 forward, 1 backward-data, 2
+// backward-filter; bf16: bf16 conv mode; h, stem: as the planners take them.
 struct ConvRoute {
   const char* family = "";  // "bf16" | "tiled" | "direct" | "gather"
   const char* kernel = "";
-  int bm = 0, bn = 0;       // block tile (rows x columns of the kernel's GEMM)
-  int z = 1;                // split-K slabs
-  bool halo = false, stem = false;
+  ConvPlan plan;
 };
-ConvRoute conv_route(const ConvShape& s, int op, bool bf16, bool epilogue, bool wcopy, int stem);
-ConvRoute conv_route_bf16(const ConvShape& s, int op, bool epilogue, int stem);
-ConvRoute conv_route_tiled(const ConvShape& s, int op, bool bf16, bool epilogue, bool wcopy);
+ConvRoute conv_route(const ConvShape& s, int op, bool bf16, const ConvHave& h, int stem);
 // bf16 MFMA convs with 64-channel K tiles and pre-laid-out bf16 weights
 // (conv_bf16.hip): forward for C, K % 64 == 0, stride-1 backward-data; the
 // bf16 weight copy and split-K slabs live in the layer workspace
@@ -122,13 +171,16 @@ void s2d_stem_input(const float* x, int N, int H, int W, int OH, int OW, void* x
                     hipStream_t st);
 void s2d_stem_weight(const float* w, int K, void* wt8, hipStream_t st);
 void s2d_stem_wgrad(const float* dw8, int K, float* gw, hipStream_t st);
-void conv_fwd_bf16(const ConvShape& s, const float* x, const float* w, const float* bias, float* y,
-                   bool relu, float* ws, hipStream_t st, const void* xb = nullptr,
-                   const void* wtb = nullptr, void* yb = nullptr,
-                   const ConvStats* stats = nullptr);
-void conv_bwd_data_bf16(const ConvShape& s, const float* dy, const float* w, float* dx, float* ws,
-                        hipStream_t st, const void* dyb = nullptr, const float* addend = nullptr,
-                        const void* wtb = nullptr, const BnBwdStats* bstats = nullptr);
+// the bf16 family's halves of conv_fwd / conv_bwd_data / conv_bwd_filter: p from
+// plan_fwd / plan_dgrad / plan_wgrad (s: the conv's own shape)
+void conv_fwd_bf16(const ConvPlan& p, const float* x, const float* w, const float* bias, float* y,
+                   bool relu, float* ws, hipStream_t st, const void* xb, const void* wtb, void* yb,
+                   const ConvStats* stats);
+void conv_bwd_data_bf16(const ConvPlan& p, const ConvShape& s, const float* dy, const float* w,
+                        float* dx, float* ws, hipStream_t st, const void* dyb, const float* addend,
+                        const void* wtb, const BnBwdStats* bstats);
+void conv_bwd_filter_bf16(const ConvPlan& p, const float* x, const float* dy, float* ws, float* dw,
+                          hipStream_t st, const void* xb, const void* dyb);
 // batched weight re-layout: jobs = device int64 [njobs][8] = {w, out, taps,
 // C, K, mode (0 bf16 forward, 1 bf16 stride-1 dgrad, 2 fp32 stride-1 dgrad:
 // flipped + ci / co transposed), first block, 0}, blocks of a job
@@ -147,27 +199,27 @@ void sgd_wcvt(float* w, const float* g, float* mom, float momentum, float gscale
               long long conv_blocks, const long long* ranges, int nranges, long long range_blocks,
               hipStream_t st);
 bool conv_bwd_filter_bf16_ok(const ConvShape& s);
-void conv_bwd_filter_bf16(const ConvShape& s, const float* x, const float* dy, float* ws,
-                          float* dw, hipStream_t st, const void* xb = nullptr,
-                          const void* dyb = nullptr);
 // LDS-tiled conv family (conv_tiled.hip), used by the launchers above for the
 // shapes it supports
 bool conv_fwd_tiled_ok(const ConvShape& s);
 bool conv_fwd_tiled_gather_ok(const ConvShape& s);  // fp32 tiled forward, flattened (kh, kw, ci)
 bool conv_bwd_data_tiled_ok(const ConvShape& s);
 bool conv_bwd_filter_tiled_ok(const ConvShape& s);
-void conv_fwd_tiled(const ConvShape& s, const float* x, const float* w, const float* bias, float* y,
-                    bool relu, float* ws, hipStream_t st, bool bf16,
-                    const ConvStats* stats = nullptr);
-// partial rows of the BatchNorm statistics the tiled forward writes (fp32 route)
-int conv_fwd_tiled_stats_rows(const ConvShape& s, bool bf16);
+// the tiled family's halves: p from plan_fwd / plan_dgrad / plan_wgrad (s: the
+// conv's own shape), bf16: the operand precision the plan was made for
+// wt: the fp32 stride-1 dgrad weight copy (conv3f_kernel forward only)
+void conv_fwd_tiled(const ConvPlan& p, const float* x, const float* w, const float* wt,
+                    const float* bias, float* y, bool relu, float* ws, hipStream_t st, bool bf16,
+                    const ConvStats* stats);
 // dy may be null when dyb (bf16 dY) is given
 // wflip (optional, fp32 stride-1 dgrad): the weights already flipped and
 // ci / co-transposed, W'[kh][kw][co][ci] = W[R-1-kh][S-1-kw][ci][co]
 // (wcvt_batch mode 2 / sgd_wcvt fp32 jobs); else a wflip launch derives them
-void conv_bwd_data_tiled(const ConvShape& s, const float* dy, const float* w, float* dx, float* ws,
-                         hipStream_t st, bool bf16, const float* addend = nullptr,
-                         const void* dyb = nullptr, const float* wflip = nullptr);
+void conv_bwd_data_tiled(const ConvPlan& p, const ConvShape& s, const float* dy, const float* w,
+                         float* dx, float* ws, hipStream_t st, bool bf16, const float* addend,
+                         const void* dyb, const float* wflip);
+void conv_bwd_filter_tiled(const ConvPlan& p, const float* x, const float* dy, float* part,
+                           float* dw, hipStream_t st, bool bf16);
 long long conv_fwd_tiled_ws_floats(const ConvShape& s, bool epilogue);
 // Tile / split plan of the tiled family.  Production runs the defaults (the
 // measured choices, docs/PERF_NOTES.md); labs (scripts/conv_lab.py) change
@@ -201,18 +253,10 @@ struct TiledPlan {
   // ResNet-18 fp32 5.462 / 5.465 -> 5.432 / 5.416 ms at 1024 -> 512 (r6_s33.steps)
   int ksplit_s2 = 512;
 };
-// fp32 3x3 / stride 1 / pad 1 halo conv (conv_tiled.hip conv3f_kernel); wt:
-// [9][K][C] read at tap 8 - t - the forward passes the stride-1 dgrad copy
-// (wflip layout), the dgrad the HWIO weights; ws: conv3f_ws_floats
+// the fp32 3x3 / stride 1 / pad 1 halo conv (conv_tiled.hip conv3f_kernel) takes s
 bool conv3f_ok(const ConvShape& s);
-long long conv3f_ws_floats(const ConvShape& s);
-void conv3f(const ConvShape& s, const float* x, const float* wt, float* y, float* ws,
-            hipStream_t st, const float* addend);
 TiledPlan& tiled_plan();
 long long conv_bwd_data_tiled_ws_floats(const ConvShape& s);
-int conv_filter_tiled_splits(const ConvShape& s);
-void conv_bwd_filter_tiled(const ConvShape& s, const float* x, const float* dy, float* part,
-                           float* dw, hipStream_t st, bool bf16);
 // mode 0: s1 = colsum(a), s2 = colsum(a^2); mode 1: s1 = colsum(a), s2 = colsum(a*b).
 // ws (chan_reduce_ws_floats) selects the deterministic bn.hip reduction;
 // null falls back to memset + atomics.

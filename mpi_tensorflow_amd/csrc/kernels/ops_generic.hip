@@ -1063,101 +1063,63 @@ static inline bool conv_fwd_direct_ok(const ConvShape& s) {
   return s.C < 32 && s.K <= 64 && s.R * s.S * s.C <= 512 &&
          (long long)s.R * s.S * s.C * s.K <= DIRECT_W_MAX;
 }
+static inline bool conv_bwd_data_direct_ok(const ConvShape& s) {
+  return s.C < 32 && (long long)s.R * s.S * s.C * s.K <= DIRECT_W_MAX && (s.K == 8 || s.K == 16);
+}
 
-// ------------------------------------------------------------ launchers ----
-// The LDS-tiled conv family (conv_tiled.hip) takes every shape it supports
-// (channel counts that are multiples of 32 / 4: all of ResNet-18 but its
-// 3-channel stem); the per-element gather engine above covers the rest
+// ------------------------------------------------------------- planners ----
+// The bf16 family (conv_bf16.hip) takes its shapes in bf16 conv mode; the
+// LDS-tiled family (conv_tiled.hip) every shape it supports (channel counts
+// that are multiples of 32 / 4: all of ResNet-18 but its 3-channel stem); the
+// direct kernels and the per-element gather engine above cover the rest
 // (LeNet-5's 3- and 6-channel layers, thin FC layers).
-void conv_fwd(const ConvShape& s, const float* x, const float* w, const float* bias, float* y,
-              bool relu, float* ws, hipStream_t st, bool bf16, const void* xb, const void* wtb,
-              void* yb, const ConvStats* stats) {
-  if (bf16 && conv_fwd_bf16_ok(s))
-    return conv_fwd_bf16(s, x, w, bias, y, relu, ws, st, xb, wtb, yb, stats);
-  if (yb) throw std::runtime_error("conv_fwd: bf16 output needs the bf16 conv family");
-  if (stats && stats->part) {  // fp32 route: the tiled forward's epilogue / slab reduction
-    if (bf16 || !(conv_fwd_tiled_ok(s) || conv_fwd_tiled_gather_ok(s)))
-      throw std::runtime_error("conv_fwd: BatchNorm statistics need the bf16 or fp32 tiled family");
-    return conv_fwd_tiled(s, x, w, bias, y, relu, ws, st, false, stats);
-  }
-  // fp32 with the stride-1 dgrad weight copy (wtb, ConvWeightCopies f32flip):
-  // the 3x3 stride-1 layers on the halo kernel
-  if (!bf16 && wtb && !bias && !relu && conv3f_ok(s))
-    return conv3f(s, x, static_cast<const float*>(wtb), y, ws, st, nullptr);
-  if (conv_fwd_tiled_ok(s)) return conv_fwd_tiled(s, x, w, bias, y, relu, ws, st, bf16);
-  if (conv_fwd_direct_ok(s)) {
-    const long long total = (long long)s.N * s.OH * s.OW * s.K;
-    const int b = grid1d(total), rl = relu ? 1 : 0;
-    switch (s.C) {
-      case 1: conv_fwd_direct_kernel<1><<<b, 256, 0, st>>>(s, x, w, bias, y, rl); break;
-      case 3: conv_fwd_direct_kernel<3><<<b, 256, 0, st>>>(s, x, w, bias, y, rl); break;
-      case 6: conv_fwd_direct_kernel<6><<<b, 256, 0, st>>>(s, x, w, bias, y, rl); break;
-      case 8: conv_fwd_direct_kernel<8><<<b, 256, 0, st>>>(s, x, w, bias, y, rl); break;
-      default: conv_fwd_direct_kernel<0><<<b, 256, 0, st>>>(s, x, w, bias, y, rl);
-    }
-    return;
-  }
+static ConvPlan engine_plan(ConvKernel k, const ConvShape& s, int bm, int bn) {
+  ConvPlan p;
+  p.kernel = k, p.run = s, p.bm = bm, p.bn = bn, p.bk = bm ? BK : 0, p.addend_ok = false;
+  return p;
+}
+
+ConvPlan plan_fwd(const ConvShape& s, bool bf16, const ConvHave& h, int stem) {
+  if (stem || (bf16 && conv_fwd_bf16_ok(s))) return plan_fwd_bf16(s, h, stem);
   // thin-input convs too big for the direct kernel (the ResNet stem): fp32
-  // MFMA tiles over the flattened (kh, kw, ci) axis
-  if (!bf16 && conv_fwd_tiled_gather_ok(s))
-    return conv_fwd_tiled(s, x, w, bias, y, relu, ws, st, false);
-  const int M = s.N * s.OH * s.OW;
-  const int blocks = ((M + CFG_F::BM - 1) / CFG_F::BM) * ((s.K + CFG_F::BN - 1) / CFG_F::BN);
-  conv_fwd_kernel<<<blocks, 256, 0, st>>>(s, x, w, bias, y, relu ? 1 : 0);
+  // MFMA tiles over the flattened (kh, kw, ci) axis; with BatchNorm statistics
+  // (the tiled forward's epilogue / slab reduction) ahead of the direct kernel
+  const bool gather = !bf16 && conv_fwd_tiled_gather_ok(s);
+  if (conv_fwd_tiled_ok(s) || (gather && (h.stats || !conv_fwd_direct_ok(s)))) {
+    ConvPlan p = plan_fwd_tiled(s, bf16, h);
+    if (bf16) p.stats_rows = 0;  // the fp32 route only
+    return p;
+  }
+  if (conv_fwd_direct_ok(s)) return engine_plan(ConvKernel::DIRECT_FWD, s, 0, 0);
+  return engine_plan(ConvKernel::GATHER_FWD, s, CFG_F::BM, CFG_F::BN);
 }
 
 // gather-engine backward-data split-K: a block's K tiles are a serial chain,
 // so with few output tiles (LeNet conv2: 196 blocks x 13 K tiles) slice K to
-// reach ~1024 blocks of >= 3 K tiles
-static void gather_data_plan(const ConvShape& s, int& z, int& kchunk) {
+// reach ~1024 blocks of >= 3 K tiles; unsplit without a workspace
+static ConvPlan gather_data_plan(const ConvShape& s, bool ws) {
+  ConvPlan p = engine_plan(ConvKernel::GATHER_DGRAD, s, CFG_D::BM, CFG_D::BN);
   const int M = s.N * s.H * s.W;
   const int blocks = ((M + CFG_D::BM - 1) / CFG_D::BM) * ((s.C + CFG_D::BN - 1) / CFG_D::BN);
   const int ktiles = (s.R * s.S * s.K + BK - 1) / BK;
-  z = (1024 + blocks - 1) / blocks;
+  int z = (1024 + blocks - 1) / blocks;
   if (z > ktiles / 3) z = ktiles / 3;
-  if (z < 1) z = 1;
-  kchunk = ((ktiles + z - 1) / z) * BK;
-  z = (ktiles * BK + kchunk - 1) / kchunk;
+  if (z < 1 || !ws) z = 1;
+  p.per = ((ktiles + z - 1) / z) * BK;
+  p.z = (ktiles * BK + p.per - 1) / p.per;
+  p.ws_floats = p.z > 1 ? (long long)p.z * M * s.C : 0;
+  return p;
 }
 
-bool conv_bwd_data_join_ok(const ConvShape& s, bool bf16) {
-  return (bf16 && conv_bwd_data_bf16_ok(s)) || conv_bwd_data_tiled_ok(s);
+ConvPlan plan_dgrad(const ConvShape& s, bool bf16, const ConvHave& h) {
+  if (bf16 && conv_bwd_data_bf16_ok(s)) return plan_dgrad_bf16(s, h);
+  if (conv_bwd_data_tiled_ok(s)) return plan_dgrad_tiled(s, bf16, h);
+  if (conv_bwd_data_direct_ok(s)) return engine_plan(ConvKernel::DIRECT_DGRAD, s, 0, 0);
+  return gather_data_plan(s, h.ws);
 }
 
-void conv_bwd_data(const ConvShape& s, const float* dy, const float* w, float* dx, float* ws,
-                   hipStream_t st, bool bf16, const void* dyb, const float* addend,
-                   const void* wtb, const BnBwdStats* bstats) {
-  if (bf16 && conv_bwd_data_bf16_ok(s))
-    return conv_bwd_data_bf16(s, dy, w, dx, ws, st, dyb, addend, wtb, bstats);
-  if (bstats && bstats->part)
-    throw std::runtime_error("conv_bwd_data: BatchNorm backward statistics need the bf16 family");
-  if (conv_bwd_data_tiled_ok(s))  // fp32: wtb = the pre-flipped fp32 weights, when given
-    return conv_bwd_data_tiled(s, dy, w, dx, ws, st, bf16, addend, dyb,
-                               bf16 ? nullptr : static_cast<const float*>(wtb));
-  if (!dy) throw std::runtime_error("conv_bwd_data: this shape needs the fp32 dY");
-  if (addend) throw std::runtime_error("conv_bwd_data: no gradient-join epilogue for this shape");
-  if (s.C < 32 && (long long)s.R * s.S * s.C * s.K <= DIRECT_W_MAX && (s.K == 8 || s.K == 16)) {
-    const int b = grid1d((long long)s.N * s.H * s.W * s.C);
-    if (s.K == 8)
-      conv_bwd_data_direct_kernel<8><<<b, 256, 0, st>>>(s, dy, w, dx);
-    else
-      conv_bwd_data_direct_kernel<16><<<b, 256, 0, st>>>(s, dy, w, dx);
-    return;
-  }
-  const int M = s.N * s.H * s.W;
-  const int blocks = ((M + CFG_D::BM - 1) / CFG_D::BM) * ((s.C + CFG_D::BN - 1) / CFG_D::BN);
-  int z, kchunk;
-  gather_data_plan(s, z, kchunk);
-  if (z > 1 && !ws) z = 1, kchunk = (s.R * s.S * s.K + BK - 1) / BK * BK;
-  conv_bwd_data_kernel<<<dim3(blocks, z), 256, 0, st>>>(s, dy, w, z > 1 ? ws : dx, kchunk);
-  if (z > 1) {
-    const long long n = (long long)M * s.C;
-    slab_sum_kernel<<<grid1d(n), 256, 0, st>>>(ws, z, n, dx);
-  }
-}
-
-int conv_filter_splits(const ConvShape& s) {
-  if (conv_bwd_filter_tiled_ok(s)) return conv_filter_tiled_splits(s);
+// gather-engine filter gradient: the slices asked for
+static int gather_filter_slices(const ConvShape& s) {
   const int Mw = s.R * s.S * s.C;
   const int tiles = ((Mw + CFG_W::BM - 1) / CFG_W::BM) * ((s.K + CFG_W::BN - 1) / CFG_W::BN);
   const int ktiles = (s.N * s.OH * s.OW + BK - 1) / BK;
@@ -1172,75 +1134,158 @@ int conv_filter_splits(const ConvShape& s) {
   return z < 1 ? 1 : z;
 }
 
+ConvPlan plan_wgrad(const ConvShape& s, bool bf16, const ConvHave& h, int stem) {
+  if (stem || (bf16 && conv_bwd_filter_bf16_ok(s))) return plan_wgrad_bf16(s, h, stem);
+  if (conv_bwd_filter_tiled_ok(s)) return plan_wgrad_tiled(s, bf16);
+  ConvPlan p = engine_plan(ConvKernel::GATHER_WGRAD, s, CFG_W::BM, CFG_W::BN);
+  const int ktiles = (s.N * s.OH * s.OW + BK - 1) / BK, z = gather_filter_slices(s);
+  p.per = ((ktiles + z - 1) / z) * BK;
+  p.z = (ktiles * BK + p.per - 1) / p.per;  // whole K tiles a slice: never more than asked for
+  p.ws_floats = (long long)p.z * s.R * s.S * s.C * s.K;  // the slab reduction runs unsplit too
+  return p;
+}
+
+// ---------------------------------------------------------------- sizes ----
+bool conv_bwd_data_join_ok(const ConvShape& s, bool bf16) {
+  return (bf16 && conv_bwd_data_bf16_ok(s)) || conv_bwd_data_tiled_ok(s);
+}
+
+int conv_fwd_stats_rows(const ConvShape& s, bool bf16) {
+  ConvHave h;
+  h.stats = true;
+  const ConvPlan p = plan_fwd(s, bf16, h);
+  if (bf16 ? !conv_kernel_bf16(p.kernel) : !conv_kernel_tiled(p.kernel))
+    throw std::runtime_error(bf16 ? "conv_fwd_stats_rows: not a bf16-family conv"
+                                  : "conv_fwd_stats_rows: not a tiled-family conv");
+  return p.stats_rows;
+}
+
+int conv_bwd_data_stats_rows(const ConvShape& s) {
+  const ConvPlan p = plan_dgrad(s, true, ConvHave());
+  return conv_kernel_bf16(p.kernel) ? p.stats_rows : 0;
+}
+
+// the slices the layer workspace is sized for
+int conv_filter_splits(const ConvShape& s) {
+  return conv_bwd_filter_tiled_ok(s) ? plan_wgrad_tiled(s, false).z : gather_filter_slices(s);
+}
+
+// one workspace for the three ops of a layer, in either conv mode (the mode
+// can change after the workspace is built) and whichever copies the calls pass
 long long conv_ws_floats(const ConvShape& s, bool fwd_epilogue) {
   long long n = (long long)conv_filter_splits(s) * s.R * s.S * s.C * s.K;
-  if (!conv_bwd_data_tiled_ok(s)) {
-    int z, kchunk;
-    gather_data_plan(s, z, kchunk);
-    if (z > 1) n = std::max(n, (long long)z * s.N * s.H * s.W * s.C);
-  }
+  if (!conv_bwd_data_tiled_ok(s)) n = std::max(n, gather_data_plan(s, true).ws_floats);
   if (conv_fwd_tiled_ok(s) || conv_fwd_tiled_gather_ok(s))
     n = std::max(n, conv_fwd_tiled_ws_floats(s, fwd_epilogue));
   if (conv_bwd_data_tiled_ok(s)) n = std::max(n, conv_bwd_data_tiled_ws_floats(s));
   return std::max(n, conv_bf16_ws_floats(s, fwd_epilogue));
 }
 
+// ------------------------------------------------------------ launchers ----
+void conv_fwd(const ConvShape& s, const float* x, const float* w, const float* bias, float* y,
+              bool relu, float* ws, hipStream_t st, bool bf16, const void* xb, const void* wtb,
+              void* yb, const ConvStats* stats) {
+  ConvHave h;
+  h.epilogue = bias || relu, h.act16 = xb, h.wcopy = wtb, h.ws = ws, h.stats = stats && stats->part;
+  const ConvPlan p = plan_fwd(s, bf16, h);
+  const bool b16 = conv_kernel_bf16(p.kernel);
+  if (yb && !b16) throw std::runtime_error("conv_fwd: bf16 output needs the bf16 conv family");
+  if (h.stats && !b16 && p.stats_rows == 0)  // (the bf16 family's launchers check theirs)
+    throw std::runtime_error("conv_fwd: BatchNorm statistics need the bf16 or fp32 tiled family");
+  if (p.ws_floats && !ws) throw std::runtime_error("conv_fwd: this route needs a workspace");
+  if (b16) return conv_fwd_bf16(p, x, w, bias, y, relu, ws, st, xb, wtb, yb, stats);
+  if (conv_kernel_tiled(p.kernel))
+    return conv_fwd_tiled(p, x, w, static_cast<const float*>(wtb), bias, y, relu, ws, st, bf16, stats);
+  if (p.kernel == ConvKernel::DIRECT_FWD) {
+    const long long total = (long long)s.N * s.OH * s.OW * s.K;
+    const int b = grid1d(total), rl = relu ? 1 : 0;
+    switch (s.C) {
+      case 1: conv_fwd_direct_kernel<1><<<b, 256, 0, st>>>(s, x, w, bias, y, rl); break;
+      case 3: conv_fwd_direct_kernel<3><<<b, 256, 0, st>>>(s, x, w, bias, y, rl); break;
+      case 6: conv_fwd_direct_kernel<6><<<b, 256, 0, st>>>(s, x, w, bias, y, rl); break;
+      case 8: conv_fwd_direct_kernel<8><<<b, 256, 0, st>>>(s, x, w, bias, y, rl); break;
+      default: conv_fwd_direct_kernel<0><<<b, 256, 0, st>>>(s, x, w, bias, y, rl);
+    }
+    return;
+  }
+  const int M = s.N * s.OH * s.OW;
+  const int blocks = ((M + p.bm - 1) / p.bm) * ((s.K + p.bn - 1) / p.bn);
+  conv_fwd_kernel<<<blocks, 256, 0, st>>>(s, x, w, bias, y, relu ? 1 : 0);
+}
+
+void conv_bwd_data(const ConvShape& s, const float* dy, const float* w, float* dx, float* ws,
+                   hipStream_t st, bool bf16, const void* dyb, const float* addend,
+                   const void* wtb, const BnBwdStats* bstats) {
+  ConvHave h;
+  h.act16 = dyb, h.dy32 = dy, h.ws = ws;
+  const ConvPlan p = plan_dgrad(s, bf16, h);
+  const bool b16 = conv_kernel_bf16(p.kernel), tiled = conv_kernel_tiled(p.kernel);
+  if (bstats && bstats->part && !b16)  // (conv_bwd_data_bf16 checks the rows of its plan)
+    throw std::runtime_error("conv_bwd_data: BatchNorm backward statistics need the bf16 family");
+  if (!dy && !b16 && !tiled) throw std::runtime_error("conv_bwd_data: this shape needs the fp32 dY");
+  if (addend && !p.addend_ok)
+    throw std::runtime_error("conv_bwd_data: no gradient-join epilogue for this shape");
+  if (p.ws_floats && !ws) throw std::runtime_error("conv_bwd_data: this route needs a workspace");
+  if (b16) return conv_bwd_data_bf16(p, s, dy, w, dx, ws, st, dyb, addend, wtb, bstats);
+  if (tiled)  // fp32: wtb = the pre-flipped fp32 weights, when given
+    return conv_bwd_data_tiled(p, s, dy, w, dx, ws, st, bf16, addend, dyb,
+                               bf16 ? nullptr : static_cast<const float*>(wtb));
+  if (p.kernel == ConvKernel::DIRECT_DGRAD) {
+    const int b = grid1d((long long)s.N * s.H * s.W * s.C);
+    if (s.K == 8)
+      conv_bwd_data_direct_kernel<8><<<b, 256, 0, st>>>(s, dy, w, dx);
+    else
+      conv_bwd_data_direct_kernel<16><<<b, 256, 0, st>>>(s, dy, w, dx);
+    return;
+  }
+  const int M = s.N * s.H * s.W;
+  const int blocks = ((M + p.bm - 1) / p.bm) * ((s.C + p.bn - 1) / p.bn);
+  conv_bwd_data_kernel<<<dim3(blocks, p.z), 256, 0, st>>>(s, dy, w, p.z > 1 ? ws : dx, p.per);
+  if (p.z > 1) {
+    const long long n = (long long)M * s.C;
+    slab_sum_kernel<<<grid1d(n), 256, 0, st>>>(ws, p.z, n, dx);
+  }
+}
+
 void conv_bwd_filter(const ConvShape& s, const float* x, const float* dy, float* part, float* dw,
                      hipStream_t st, bool bf16, const void* xb,
                      const void* dyb) {
-  if (bf16 && conv_bwd_filter_bf16_ok(s))
-    return conv_bwd_filter_bf16(s, x, dy, part, dw, st, xb, dyb);
-  if (conv_bwd_filter_tiled_ok(s)) return conv_bwd_filter_tiled(s, x, dy, part, dw, st, bf16);
+  ConvHave h;
+  h.act16 = xb, h.dy16 = dyb, h.ws = part;
+  const ConvPlan p = plan_wgrad(s, bf16, h);
+  if (p.ws_floats && !part) throw std::runtime_error("conv_bwd_filter: this route needs a workspace");
+  if (conv_kernel_bf16(p.kernel)) return conv_bwd_filter_bf16(p, x, dy, part, dw, st, xb, dyb);
+  if (conv_kernel_tiled(p.kernel)) return conv_bwd_filter_tiled(p, x, dy, part, dw, st, bf16);
   const int Mw = s.R * s.S * s.C;
-  const int tiles = ((Mw + CFG_W::BM - 1) / CFG_W::BM) * ((s.K + CFG_W::BN - 1) / CFG_W::BN);
-  const int ktiles = (s.N * s.OH * s.OW + BK - 1) / BK;
-  const int z = conv_filter_splits(s);
-  const int kchunk = ((ktiles + z - 1) / z) * BK;
-  const int zz = (ktiles * BK + kchunk - 1) / kchunk;
-  conv_bwd_filter_kernel<<<tiles * zz, 256, 0, st>>>(s, x, dy, part, kchunk);
+  const int tiles = ((Mw + p.bm - 1) / p.bm) * ((s.K + p.bn - 1) / p.bn);
+  conv_bwd_filter_kernel<<<tiles * p.z, 256, 0, st>>>(s, x, dy, part, p.per);
   const long long n = (long long)Mw * s.K;
-  if (zz >= 32)
-    slab_sum_wide_kernel<<<(int)((n + 15) / 16), 256, 0, st>>>(part, zz, n, dw);
+  if (p.z >= 32)
+    slab_sum_wide_kernel<<<(int)((n + 15) / 16), 256, 0, st>>>(part, p.z, n, dw);
   else
-    slab_sum_kernel<<<grid1d(n), 256, 0, st>>>(part, zz, n, dw);
+    slab_sum_kernel<<<grid1d(n), 256, 0, st>>>(part, p.z, n, dw);
 }
 
-// follows conv_fwd / conv_bwd_data / conv_bwd_filter above (without BatchNorm
-// statistics, which the fp32 forward sends to the tiled kernels regardless)
-ConvRoute conv_route(const ConvShape& s, int op, bool bf16, bool epilogue, bool wcopy, int stem) {
+// the plan of a call with the names of its kernel, in the order of ConvKernel
+ConvRoute conv_route(const ConvShape& s, int op, bool bf16, const ConvHave& h, int stem) {
+  static const char* const names[][2] = {
+      {"bf16", "fwd_kernel"}, {"bf16", "fwd_kernel/ex2"}, {"bf16", "conv3_kernel"},
+      {"bf16", "dgrad3s2_kernel"}, {"bf16", "wgrad_kernel"}, {"bf16", "wgrad3_kernel"},
+      {"bf16", "fwd_kernel/StemLoader"}, {"bf16", "fwd_kernel/S2dLoaderPre"},
+      {"bf16", "fwd_kernel/S2dLoader"}, {"bf16", "wgrad_kernel/StemWgLoader"},
+      {"tiled", "fwd_kernel"}, {"tiled", "fwd_kernel/gather"}, {"tiled", "conv3f_kernel"},
+      {"tiled", "data_kernel"}, {"tiled", "data_b16_kernel"}, {"tiled", "dgrad3s2f_kernel"},
+      {"tiled", "filter_kernel"}, {"tiled", "filter_gather_kernel"},
+      {"direct", "conv_fwd_direct_kernel"}, {"direct", "conv_bwd_data_direct_kernel"},
+      {"gather", "conv_fwd_kernel"}, {"gather", "conv_bwd_data_kernel"},
+      {"gather", "conv_bwd_filter_kernel"}};
+  static_assert(sizeof(names) / sizeof(names[0]) == (size_t)ConvKernel::COUNT,
+                "one (family, kernel) row per ConvKernel, in its order");
   if (op < 0 || op > 2) throw std::runtime_error("conv_route: op must be 0 (fwd), 1 (dgrad), 2 (wgrad)");
-  if (stem) return conv_route_bf16(s, op, epilogue, stem);
+  if (stem && op == 1) throw std::runtime_error("conv_route: the stem has no backward-data");
   ConvRoute r;
-  if (op == 0) {
-    if (bf16 && conv_fwd_bf16_ok(s)) return conv_route_bf16(s, op, epilogue, 0);
-    if (!bf16 && wcopy && !epilogue && conv3f_ok(s)) return conv_route_tiled(s, op, bf16, epilogue, wcopy);
-    if (conv_fwd_tiled_ok(s)) return conv_route_tiled(s, op, bf16, epilogue, false);
-    if (conv_fwd_direct_ok(s)) {
-      r.family = "direct", r.kernel = "conv_fwd_direct_kernel";
-      return r;
-    }
-    if (!bf16 && conv_fwd_tiled_gather_ok(s)) return conv_route_tiled(s, op, false, epilogue, false);
-    r.family = "gather", r.kernel = "conv_fwd_kernel", r.bm = CFG_F::BM, r.bn = CFG_F::BN;
-    return r;
-  }
-  if (op == 1) {
-    if (bf16 && conv_bwd_data_bf16_ok(s)) return conv_route_bf16(s, op, false, 0);
-    if (conv_bwd_data_tiled_ok(s)) return conv_route_tiled(s, op, bf16, false, wcopy);
-    if (s.C < 32 && (long long)s.R * s.S * s.C * s.K <= DIRECT_W_MAX && (s.K == 8 || s.K == 16)) {
-      r.family = "direct", r.kernel = "conv_bwd_data_direct_kernel";
-      return r;
-    }
-    int kchunk;
-    gather_data_plan(s, r.z, kchunk);
-    r.family = "gather", r.kernel = "conv_bwd_data_kernel", r.bm = CFG_D::BM, r.bn = CFG_D::BN;
-    return r;
-  }
-  if (bf16 && conv_bwd_filter_bf16_ok(s)) return conv_route_bf16(s, op, false, 0);
-  if (conv_bwd_filter_tiled_ok(s)) return conv_route_tiled(s, op, bf16, false, false);
-  const int ktiles = (s.N * s.OH * s.OW + BK - 1) / BK;
-  const int kchunk = ((ktiles + conv_filter_splits(s) - 1) / conv_filter_splits(s)) * BK;
-  r.family = "gather", r.kernel = "conv_bwd_filter_kernel", r.bm = CFG_W::BM, r.bn = CFG_W::BN;
-  r.z = (ktiles * BK + kchunk - 1) / kchunk;
+  r.plan = op == 0 ? plan_fwd(s, bf16, h, stem) : op == 1 ? plan_dgrad(s, bf16, h) : plan_wgrad(s, bf16, h, stem);
+  r.family = names[(int)r.plan.kernel][0], r.kernel = names[(int)r.plan.kernel][1];
   return r;
 }
 

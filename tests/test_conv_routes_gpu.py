@@ -3,8 +3,11 @@ the direct kernels of ops_generic.hip), route by route, against the references
 of tests/helpers/conv_ref.py on the kernels' own operands.
 
 Every case names the kernel, tile and split-K depth it is there for and
-asserts them through `ops.conv_route` (the launchers' own plans), so a plan
-change cannot move a case onto another kernel and leave one untested.  The
+asserts them through `ops.conv_route`, which returns the plan that the
+launcher of the same call executes (one planner per op, gops::plan_fwd /
+plan_dgrad / plan_wgrad; its keyword flags say which operand copies,
+statistics and workspace the call passes), so a plan change cannot move a case
+onto another kernel and leave one untested.  The
 kernels are driven through Fn.conv2d as the engine drives them: bf16 twins
 attached to the inputs, bf16 dY where the route takes one, BatchNorm links
 for the statistics epilogues, a GradJoin for the addend, the weight copies of
@@ -389,47 +392,131 @@ def test_k192_forward_stays_inside_its_output(cuda_dev):
     assert R.exact_diff(buf[:M * K].reshape(N, H, H, K), o["refs"]["fwd"][0])[0] == 0
 
 
+# ------------------------- routes chosen by what the call passes, exact ----
+def _direct(cuda_dev, shape, seed, also=None):
+    """ConvShape, exact operands on the device and a zeroed workspace, for ops called directly."""
+    ops = _ops()
+    N, H, W, C, K, Rr, stride, pad = shape
+    sh = ops.ConvShape(N, H, W, C, K, Rr, Rr, stride, pad)
+    o = R.gen_exact(seed, *shape, also=also)
+    R.assert_exact(*(r[1].max() for r in o["refs"].values()))
+    d = {k: o[k].to(cuda_dev) for k in ("x", "w", "dy")}
+    ws = torch.zeros(max(int(ops.conv_ws_floats(sh, False)), 4), device=cuda_dev)
+    return ops, sh, o, d, ws
+
+
+def test_fp32_forward_with_statistics_leaves_the_halo_kernel(cuda_dev):
+    """fp32 forward with the weight copy passed: conv3f_kernel, but fwd_kernel
+    once BatchNorm statistics are wanted (the forward of most 3x3 layers of
+    ResNet-18 in fp32 training); output and both statistics sums to the bit."""
+    from mpi_tensorflow_amd.ops import ptr, stream_handle
+
+    shape = (2, 14, 14, 64, 64, 3, 1, 1)
+    K = shape[4]
+    g = torch.Generator().manual_seed(41)
+    shift = torch.randint(-2, 3, (K,), generator=g).to(F32)
+    ops, sh, o, d, ws = _direct(
+        cuda_dev, shape, 81, also=lambda o: float(R.stats_fwd(o["refs"]["fwd"][0], shift, dt=F32)[3].max()))
+    assert ops.conv_route(sh, "fwd", False, wcopy=True)["kernel"] == "conv3f_kernel"
+    r = ops.conv_route(sh, "fwd", False, wcopy=True, stats=True)
+    assert (r["family"], r["kernel"]) == ("tiled", "fwd_kernel")
+    rows = ops.conv_fwd_stats_rows(sh, False)
+    assert r["stats_rows"] == rows > 0
+    wp = _param(d["w"])
+    Fn.ConvWeightCopies({"w": wp}, cuda_dev, kind="f32flip").refresh()
+    assert wp.wtb_d is not None
+    y = torch.empty(sh.N, sh.OH, sh.OW, K, device=cuda_dev)
+    part = torch.zeros(2 * K * rows, device=cuda_dev)
+    sg = shift.to(cuda_dev)
+    ops.conv_fwd(sh, ptr(d["x"]), ptr(d["w"]), 0, ptr(y), False, ptr(ws), stream_handle(), False, 0,
+                 ptr(wp.wtb_d), 0, ptr(part), rows, ptr(sg))
+    torch.cuda.synchronize()
+    yc = y.cpu()
+    assert R.exact_diff(yc, o["refs"]["fwd"][0])[0] == 0
+    g1, g2 = R.part_sums(part, K, rows)
+    s1, _, s2, S2, _ = R.stats_fwd(yc, shift, dt=F32)
+    R.assert_exact(S2.max())
+    assert torch.equal(g1.to(F32), s1) and torch.equal(g2.to(F32), s2)
+
+
+def test_bf16_mode_without_operand_copies(cuda_dev):
+    """bf16 conv mode with a bf16 operand copy left out: the forward without xb
+    runs fwd_kernel (not conv3_kernel), the 3x3 stride-2 dgrad with the fp32 dY
+    alone the tiled family's data_kernel, the filter gradient without dyb
+    wgrad_kernel (not wgrad3_kernel); each to the bit."""
+    from mpi_tensorflow_amd.ops import ptr, stream_handle
+
+    st = stream_handle()
+    ops, sh, o, d, ws = _direct(cuda_dev, (2, 14, 14, 64, 64, 3, 1, 1), 82)
+    assert ops.conv_route(sh, "fwd", True)["kernel"] == "conv3_kernel"
+    r = ops.conv_route(sh, "fwd", True, act16=False)
+    assert (r["family"], r["kernel"]) == ("bf16", "fwd_kernel")
+    y = torch.empty(sh.N, sh.OH, sh.OW, sh.K, device=cuda_dev)
+    ops.conv_fwd(sh, ptr(d["x"]), ptr(d["w"]), 0, ptr(y), False, ptr(ws), st, True)
+    torch.cuda.synchronize()
+    assert R.exact_diff(y, o["refs"]["fwd"][0])[0] == 0
+
+    ops, sh, o, d, ws = _direct(cuda_dev, (2, 14, 14, 64, 128, 3, 2, 1), 83)
+    assert ops.conv_route(sh, "dgrad", True)["kernel"] == "dgrad3s2_kernel"
+    r = ops.conv_route(sh, "dgrad", True, act16=False)
+    assert (r["family"], r["kernel"]) == ("tiled", "data_kernel")
+    dx = torch.empty(sh.N, sh.H, sh.W, sh.C, device=cuda_dev)
+    ops.conv_bwd_data(sh, ptr(d["dy"]), ptr(d["w"]), ptr(dx), ptr(ws), st, True)
+    torch.cuda.synchronize()
+    assert R.exact_diff(dx, o["refs"]["dgrad"][0])[0] == 0
+
+    ops, sh, o, d, ws = _direct(cuda_dev, (4, 14, 14, 64, 64, 3, 1, 1), 84)
+    assert ops.conv_route(sh, "wgrad", True)["kernel"] == "wgrad3_kernel"
+    r = ops.conv_route(sh, "wgrad", True, dy16=False)
+    assert (r["family"], r["kernel"]) == ("bf16", "wgrad_kernel")
+    xb = d["x"].to(BF)
+    dw = torch.empty_like(d["w"])
+    ops.conv_bwd_filter(sh, ptr(d["x"]), ptr(d["dy"]), ptr(ws), ptr(dw), st, True, ptr(xb), 0)
+    torch.cuda.synchronize()
+    assert R.exact_diff(dw, o["refs"]["wgrad"][0])[0] == 0
+
+
+def test_fp32_filter_gradient_k_tile_depth(cuda_dev):
+    """The fp32 64 x 128 filter tiles on 16-pixel K tiles (TiledPlan wg_bk16)
+    and on 32-pixel ones: the route names the depth, the bits are equal."""
+    from mpi_tensorflow_amd.ops import ptr, stream_handle
+
+    ops, sh, o, d, ws = _direct(cuda_dev, (4, 28, 28, 64, 128, 3, 2, 1), 85)
+    plan = ops.get_tiled_plan()
+    got = []
+    try:
+        for on, bk in ((True, 16), (False, 32)):
+            p = ops.get_tiled_plan()
+            p.wg_bk16 = on
+            ops.set_tiled_plan(p)
+            r = ops.conv_route(sh, "wgrad", False)
+            assert (r["kernel"], r["bm"], r["bn"], r["bk"]) == ("filter_kernel", 64, 128, bk)
+            dw = torch.empty_like(d["w"])
+            ops.conv_bwd_filter(sh, ptr(d["x"]), ptr(d["dy"]), ptr(ws), ptr(dw), stream_handle())
+            torch.cuda.synchronize()
+            assert R.exact_diff(dw, o["refs"]["wgrad"][0])[0] == 0
+            got.append(dw.cpu())
+    finally:
+        ops.set_tiled_plan(plan)
+    assert torch.equal(got[0].view(torch.int32), got[1].view(torch.int32))
+
+
 # ----------------------------------------- fp32 tiled family, exact mode ----
 # the shape lists of tests/test_generic_ops_gpu.py (test_conv_fwd_bwd,
 # test_fp32_halo_conv3x3_fwd_and_dgrad, test_fp32_filter_grad_xcd_slice_order,
 # test_fp32_dgrad3s2_halo) with their TiledPlan variants; (shape, relu, bias,
 # weight copy, plan fields, routes) - routes as (family, kernel, bm, bn, z)
-def _halo_variants():
-    return [dict(halo_f32=True, halo_f32_wide=True, halo_f32_bm=64, halo_f32_ch=16),
-            dict(halo_f32=True, halo_f32_wide=True, halo_f32_bm=128, halo_f32_ch=16),
-            dict(halo_f32=True, halo_f32_wide=False, halo_f32_bm=64, halo_f32_ch=32),
-            dict(halo_f32=True, halo_f32_wide=False, halo_f32_bm=128, halo_f32_ch=32),
-            dict(halo_f32=True, halo_f32_wide=False, halo_f32_bm=64, halo_f32_ch=16),
-            dict(halo_f32=True, halo_f32_wide=False, halo_f32_bm=128, halo_f32_ch=16),
-            dict(halo_f32=True, halo_f32_wide=False, halo_f32_bm=0, halo_f32_ch=16),
-            dict(halo_f32=True, halo_f32_wide=False, halo_f32_bm=64, halo_f32_ch=16, halo_f32_small=True),
-            dict(halo_f32=False, halo_f32_wide=False, halo_f32_bm=64, halo_f32_ch=32)]
-
-
-FP32_SHAPES = [  # N, H, W, C, K, R, stride, pad, relu, bias
-    (4, 9, 7, 5, 6, 3, 1, 1, True, True), (4, 12, 12, 8, 16, 3, 2, 1, False, False),
-    (2, 16, 16, 3, 64, 7, 2, 3, False, False), (3, 20, 18, 3, 64, 7, 2, 3, True, True),
-    (2, 15, 15, 5, 72, 5, 1, 2, False, False), (3, 8, 8, 16, 32, 1, 2, 0, False, False),
-    (5, 1, 1, 40, 70, 1, 1, 0, True, True), (4, 32, 32, 3, 6, 5, 1, 0, True, True),
-    (4, 14, 14, 6, 16, 5, 1, 0, True, True), (3, 10, 11, 4, 8, 3, 1, 1, True, False),
-    (2, 14, 14, 64, 64, 3, 1, 1, False, False), (2, 14, 14, 64, 128, 3, 2, 1, False, False),
-    (2, 13, 13, 64, 128, 1, 2, 0, False, False), (3, 7, 7, 256, 96, 3, 1, 1, True, True),
-    (2, 9, 9, 32, 36, 5, 2, 2, False, True), (8, 1, 1, 512, 12, 1, 1, 0, False, True),
-    (10, 56, 56, 64, 64, 3, 1, 1, False, False)]
-HALO_SHAPES = [(8, 56, 56, 64, 64), (2, 56, 56, 64, 64), (4, 14, 14, 256, 256), (4, 28, 28, 128, 128),
-               (3, 7, 7, 512, 512), (2, 13, 9, 32, 64)]
-XCD_SHAPES = [(8, 56, 64, 64, 3, 1, 1), (4, 28, 64, 128, 3, 2, 1), (4, 28, 64, 128, 1, 2, 0),
-              (2, 40, 3, 64, 7, 2, 3)]
-S2_SHAPES = [(4, 56, 64, 128), (2, 28, 128, 256), (3, 14, 256, 512), (2, 10, 64, 32)]
-XCD_VARIANTS = [dict(wg_xcd=True, wg_bk16=False, wg_bk16_64=False),
-                dict(wg_xcd=False, wg_bk16=False, wg_bk16_64=False),
-                dict(wg_xcd=False, wg_bk16=True, wg_bk16_64=True)]
+_cspec = importlib.util.spec_from_file_location("conv_plan_cases", os.path.join(_HERE, "helpers", "conv_plan_cases.py"))
+PC = importlib.util.module_from_spec(_cspec)
+_cspec.loader.exec_module(PC)
+_halo_variants, FP32_SHAPES, HALO_SHAPES = PC._halo_variants, PC.FP32_SHAPES, PC.HALO_SHAPES
+XCD_SHAPES, S2_SHAPES, XCD_VARIANTS, S2_VARIANTS = PC.XCD_SHAPES, PC.S2_SHAPES, PC.XCD_VARIANTS, PC.S2_VARIANTS
 
 FP32_RUNS = ([(s[:8], s[8], s[9], False, [{}]) for s in FP32_SHAPES] +
              [((N, H, W, C, K, 3, 1, 1), False, False, True, _halo_variants()) for N, H, W, C, K in HALO_SHAPES] +
              [((N, H, H, C, K, Rr, st, pd), False, False, False, XCD_VARIANTS)
               for N, H, C, K, Rr, st, pd in XCD_SHAPES] +
-             [((N, H, H, C, K, 3, 2, 1), False, False, False, [dict(halo_f32_s2=True), dict(halo_f32_s2=False)])
+             [((N, H, H, C, K, 3, 2, 1), False, False, False, S2_VARIANTS)
               for N, H, C, K in S2_SHAPES])
 
 
