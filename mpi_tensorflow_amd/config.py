@@ -87,6 +87,9 @@ AUGMENT_FILL = {"mnist_cnn": -0.5, "lenet5": 0.0, "resnet18": 0.0}
 # else is a file), and the largest test-time-augmentation shift (shift:3 with
 # flip is already 98 forwards per row)
 PREDICT_SPLITS = ("test", "val")
+# the synthetic ResNet-18 shard of a rank: (train rows, test rows); the trainer
+# and `--predict test` generate the same rows from it
+RESNET_SYNTH_ROWS = (512, 256)
 MAX_TTA_SHIFT = 3
 # --predict-weights: the trained weights, or their moving average (--ema)
 PREDICT_WEIGHTS = ("raw", "ema")
@@ -398,9 +401,9 @@ class TrainConfig:
         if self.ema is not None:
             parse_ema(self.ema)
             if self.model == "resnet18":
-                raise ValueError("--ema does not support --model resnet18 (its forward lives in "
-                                 "the autograd engine, and its BatchNorm statistics would need "
-                                 "averaging too); use mnist_cnn or lenet5")
+                raise ValueError("--ema does not support --model resnet18: averaging its "
+                                 "BatchNorm statistics inside the training step is a separate "
+                                 "piece of work; use mnist_cnn or lenet5")
         self.label_smoothing = check_label_smoothing(self.label_smoothing)
         if self.mix is not None:
             parse_mix(self.mix)
@@ -429,9 +432,11 @@ class TrainConfig:
                              "--label-smoothing); a prediction has no target to soften")
         if not self.resume:
             raise ValueError("--predict needs the checkpoint to predict with: --resume PATH")
-        if self.model == "resnet18":
-            raise ValueError("--predict does not support --model resnet18 (its forward lives in "
-                             "the autograd engine); use mnist_cnn or lenet5")
+        if (self.model == "resnet18" and self.dtype == "fp32" and self.backend != "torch"
+                and self.device != "cpu"):
+            raise ValueError("--predict --model resnet18: the native inference forward is bf16, "
+                             "pass --dtype bf16 (fp32 runs on the torch path only: --backend "
+                             "torch or --device cpu)")
         if not 1 <= self.predict_topk <= NUM_CLASSES:
             raise ValueError(f"--predict-topk must be in [1, {NUM_CLASSES}], got "
                              f"{self.predict_topk}")

@@ -21,6 +21,7 @@
 #include "lenet_executor.h"
 #include "mnist_executor.h"
 #include "rccl_comm.h"
+#include "resnet_infer.h"
 #include "shm_comm.h"
 #include "xgmi_comm.h"
 
@@ -659,6 +660,42 @@ PYBIND11_MODULE(_C, m) {
     gops::wcvt_batch(P<const long long>(jobs), njobs, nblocks, S(st));
     check_launch();
   });
+  // the inference forward's ops: the affine-epilogue convs run the plan of
+  // conv_route(shape, "fwd", True) (stem: stem=2), which the caller can read
+  g.def("conv_fwd_affine_bf16", [](const gops::ConvShape& s, uintptr_t xb, uintptr_t wtb,
+                                   uintptr_t a, uintptr_t b, uintptr_t res, bool relu, uintptr_t yb,
+                                   uintptr_t ws, uintptr_t st) {
+    if (!gops::conv_fwd_bf16_ok(s))
+      throw std::runtime_error("conv_fwd_affine_bf16: C and K must be multiples of 64");
+    gops::conv_fwd_affine_bf16(gops::plan_fwd_bf16(s, gops::ConvHave{}), P<const void>(xb),
+                               P<const void>(wtb), P<const float>(a), P<const float>(b),
+                               P<const void>(res), relu, P<void>(yb), P<float>(ws), S(st));
+    check_launch();
+  });
+  g.def("conv_fwd_s2d_stem_affine_bf16", [](const gops::ConvShape& si, uintptr_t xs, uintptr_t wt8,
+                                            uintptr_t a, uintptr_t b, bool relu, uintptr_t yb,
+                                            uintptr_t st) {
+    gops::conv_fwd_s2d_stem_affine_bf16(si, P<const void>(xs), P<const void>(wt8),
+                                        P<const float>(a), P<const float>(b), relu, P<void>(yb),
+                                        S(st));
+    check_launch();
+  });
+  g.def("bn_fold", [](uintptr_t jobs, int njobs, int total, float eps, uintptr_t out,
+                      uintptr_t st) {
+    gops::bn_fold(P<const long long>(jobs), njobs, total, eps, P<float>(out), S(st));
+    check_launch();
+  });
+  g.def("maxpool_infer_b16", [](const gops::PoolShape& p, uintptr_t xb, uintptr_t yb,
+                                uintptr_t st) {
+    gops::maxpool_infer_b16(p, P<const void>(xb), P<void>(yb), S(st));
+    check_launch();
+  });
+  g.def("avgpool_fc", [](uintptr_t xb, uintptr_t w, uintptr_t bias, uintptr_t logits, int M,
+                         int HW, int C, int N, uintptr_t st) {
+    gops::avgpool_fc(P<const void>(xb), P<const float>(w), P<const float>(bias), P<float>(logits),
+                     M, HW, C, N, S(st));
+    check_launch();
+  });
   g.def("conv_ws_floats", &gops::conv_ws_floats);
   g.def("conv_filter_splits", &gops::conv_filter_splits);
   // read-only: the plan the launchers execute for a call (gops::conv_route) -
@@ -1104,6 +1141,33 @@ PYBIND11_MODULE(_C, m) {
       .def_static("eval_chunk", [](const LenetPtrs& p, uintptr_t x, uintptr_t y, int M,
                                    uintptr_t logits, uintptr_t errors, uintptr_t s) {
         LenetExecutor::eval_chunk(p, x, y, M, logits, errors, S(s));
+        check_launch();
+      });
+
+  py::class_<ResnetInferPtrs>(m, "ResnetInferPtrs")
+      .def(py::init<>())
+      .def_readwrite("H", &ResnetInferPtrs::H)
+      .def_readwrite("W", &ResnetInferPtrs::W)
+      .def_readwrite("classes", &ResnetInferPtrs::classes)
+      .def_readwrite("wt8", &ResnetInferPtrs::wt8)
+      .def_readwrite("wt", &ResnetInferPtrs::wt)
+      .def_readwrite("fold", &ResnetInferPtrs::fold)
+      .def_readwrite("fold_total", &ResnetInferPtrs::fold_total)
+      .def_readwrite("fold_off", &ResnetInferPtrs::fold_off)
+      .def_readwrite("fc_w", &ResnetInferPtrs::fc_w)
+      .def_readwrite("fc_b", &ResnetInferPtrs::fc_b);
+  py::class_<ResnetInfer>(m, "ResnetInfer")
+      .def_static("max_rows", &ResnetInfer::max_rows)
+      // bytes of the three bf16 activation buffers and of the fp32 split-K
+      // workspace that serve every chunk of up to `rows` rows
+      .def_static("ws_bytes", [](const ResnetInferPtrs& p, int rows) {
+        const ResnetInferSizes z = ResnetInfer::ws_sizes(p, rows);
+        return py::make_tuple(2 * z.act[0], 2 * z.act[1], 2 * z.act[2], 4 * z.ws_floats);
+      })
+      .def_static("eval_chunk", [](const ResnetInferPtrs& p, uintptr_t x, int rows, uintptr_t act0,
+                                   uintptr_t act1, uintptr_t act2, uintptr_t ws,
+                                   long long ws_floats, uintptr_t logits, uintptr_t s) {
+        ResnetInfer::eval_chunk(p, x, rows, act0, act1, act2, ws, ws_floats, logits, S(s));
         check_launch();
       });
 

@@ -49,6 +49,16 @@ struct BnBwdStats {
   const float* rstd = nullptr;
   int relu = 0;
 };
+// Inference epilogue of a bf16-family forward conv (conv_fwd_affine_bf16): a
+// folded BatchNorm, the residual and the ReLU, in fp32 and in this order:
+//   v = fmaf(acc, a[co], b[co]);  v += float(res[m][co]) (res bf16, optional);
+//   v = max(v, 0) (relu);  yb[m][co] = bf16(v)
+struct ConvAffine {
+  const float* a = nullptr;
+  const float* b = nullptr;
+  const void* res = nullptr;  // bf16 [M][K]
+  int relu = 0;
+};
 // The launch decision of one conv call, as a value: the planners below build
 // it, the launchers execute it, conv_route prints it and the size queries
 // read its workspace and statistics fields.
@@ -179,6 +189,31 @@ void conv_fwd_bf16(const ConvPlan& p, const float* x, const float* w, const floa
 void conv_bwd_data_bf16(const ConvPlan& p, const ConvShape& s, const float* dy, const float* w,
                         float* dx, float* ws, hipStream_t st, const void* dyb, const float* addend,
                         const void* wtb, const BnBwdStats* bstats);
+// Inference forward: the plan of plan_fwd_bf16(s, ConvHave{}) (B16_CONV3 or
+// B16_FWD) on bf16 activations xb and the forward weight copy wtb, with the
+// ConvAffine epilogue into the bf16 output yb.  A split plan (p.z > 1) writes
+// its fp32 slabs into ws (p.ws_floats floats) and a reduction sums them in
+// slab order, then applies the same epilogue.  Throws on any other plan.
+void conv_fwd_affine_bf16(const ConvPlan& p, const void* xb, const void* wtb, const float* a,
+                          const float* b, const void* res, bool relu, void* yb, float* ws,
+                          hipStream_t st);
+// ... and the space-to-depth stem (conv_fwd_s2d_stem_bf16's operands), no residual
+void conv_fwd_s2d_stem_affine_bf16(const ConvShape& si, const void* xs, const void* wt8,
+                                   const float* a, const float* b, bool relu, void* yb,
+                                   hipStream_t st);
+// resnet_infer.hip: the kernels around the affine convs of the ResNet-18
+// inference forward.
+// bn_fold: every BatchNorm of a model folded to a = g / sqrtf(rv + eps), b =
+// fmaf(-rm, a, beta) in ONE launch; jobs = device int64 [njobs][8] = {g, beta, rm, rv,
+// C, offset, 0, 0}; out [2][total]: a at out[offset + c], b at out[total +
+// offset + c]
+void bn_fold(const long long* jobs, int njobs, int total, float eps, float* out, hipStream_t st);
+// max pool of a bf16 NHWC tensor into a bf16 one (no argmax, no fp32 output); C % 8 == 0
+void maxpool_infer_b16(const PoolShape& p, const void* xb, void* yb, hipStream_t st);
+// logits [M][N] = (mean over the HW pixels of xb [M][HW][C] bf16) W [C][N] + bias:
+// the pixel sum first (pixel order), times 1 / HW, then the FC; fp32
+void avgpool_fc(const void* xb, const float* w, const float* bias, float* logits, int M, int HW,
+                int C, int N, hipStream_t st);
 void conv_bwd_filter_bf16(const ConvPlan& p, const float* x, const float* dy, float* ws, float* dw,
                           hipStream_t st, const void* xb, const void* dyb);
 // batched weight re-layout: jobs = device int64 [njobs][8] = {w, out, taps,

@@ -1,0 +1,154 @@
+#include "resnet_infer.h"
+
+#include <algorithm>
+#include <stdexcept>
+
+#include "kernels/ops_generic.h"
+
+namespace {
+
+using gops::ConvShape;
+
+template <class T>
+inline T* P(uintptr_t v) {
+  return reinterpret_cast<T*>(v);
+}
+
+ConvShape conv_shape(int N, int H, int W, int C, int K, int R, int stride, int pad) {
+  return ConvShape{N, H, W, C, K, R, R, stride, pad, (H + 2 * pad - R) / stride + 1,
+                   (W + 2 * pad - R) / stride + 1};
+}
+
+struct Block {
+  ConvShape c1, c2, ds;
+  bool down;
+};
+
+// the layer shapes of a chunk of m rows (models/generic.py ResNet18)
+struct Net {
+  ConvShape stem, s2d;  // the 7x7 / 2 / 3 conv and its 4x4 space-to-depth form
+  gops::PoolShape pool;
+  Block blocks[8];
+  int fh, fw;  // the final feature map
+  Net(const ResnetInferPtrs& p, int m) {
+    stem = conv_shape(m, p.H, p.W, 3, 64, 7, 2, 3);
+    s2d = ConvShape{m, stem.OH + 3, stem.OW + 3, 16, 64, 4, 4, 1, 0, stem.OH, stem.OW};
+    pool = gops::PoolShape{m, stem.OH, stem.OW, 64, 3, 2, 1, (stem.OH + 2 - 3) / 2 + 1,
+                           (stem.OW + 2 - 3) / 2 + 1};
+    const int stages[4][2] = {{64, 1}, {128, 2}, {256, 2}, {512, 2}};
+    int h = pool.OH, w = pool.OW, cin = 64, b = 0;
+    for (const auto& st : stages)
+      for (int bi = 0; bi < 2; ++bi, ++b) {
+        const int c = st[0], s = bi == 0 ? st[1] : 1;
+        Block& k = blocks[b];
+        k.down = s != 1 || cin != c;
+        k.c1 = conv_shape(m, h, w, cin, c, 3, s, 1);
+        k.c2 = conv_shape(m, k.c1.OH, k.c1.OW, c, c, 3, 1, 1);
+        k.ds = conv_shape(m, h, w, cin, c, 1, s, 0);
+        h = k.c1.OH, w = k.c1.OW, cin = c;
+      }
+    fh = h, fw = w;
+  }
+};
+
+long long out_elems(const ConvShape& s) { return (long long)s.N * s.OH * s.OW * s.K; }
+
+void check(const ResnetInferPtrs& p, int m) {
+  if (p.H < 32 || p.W < 32) throw std::runtime_error("ResnetInfer: the image must be 32 x 32 or larger");
+  if (m < 1 || m > ResnetInfer::max_rows(p))
+    throw std::runtime_error("ResnetInfer: chunk rows outside [1, max_rows]");
+}
+
+// the convs of a chunk, in launch order
+template <class F>
+void each_conv(const Net& n, F f) {
+  for (const Block& b : n.blocks) {
+    if (b.down) f(b.ds);
+    f(b.c1);
+    f(b.c2);
+  }
+}
+
+// workspace floats of a chunk of exactly m rows.  NOT monotone in m: small
+// chunks split K (slabs behind the weight-copy region) where large ones do not
+long long ws_floats_at(const ResnetInferPtrs& p, int m) {
+  long long f = 0;
+  each_conv(Net(p, m), [&](const ConvShape& s) {
+    f = std::max(f, gops::plan_fwd_bf16(s, gops::ConvHave{}).ws_floats);
+  });
+  return f;
+}
+
+void conv(const ConvShape& s, const void* x, uintptr_t wt, const ResnetInferPtrs& p, int bn,
+          const void* res, bool relu, void* y, float* ws, hipStream_t st) {
+  const float* fold = P<const float>(p.fold);
+  const int off = p.fold_off[bn];
+  gops::conv_fwd_affine_bf16(gops::plan_fwd_bf16(s, gops::ConvHave{}), x, P<const void>(wt),
+                             fold + off, fold + p.fold_total + off, res, relu, y, ws, st);
+}
+
+}  // namespace
+
+int ResnetInfer::max_rows(const ResnetInferPtrs& p) {
+  const Net n(p, 1);
+  const long long per = std::max((long long)n.stem.OH * n.stem.OW * 64,
+                                 (long long)n.s2d.H * n.s2d.W * 16);
+  return (int)std::min<long long>(((1LL << 31) - 1) / per, 1 << 20);
+}
+
+ResnetInferSizes ResnetInfer::ws_sizes(const ResnetInferPtrs& p, int m) {
+  check(p, m);
+  const Net n(p, m);
+  ResnetInferSizes z;
+  long long blk = (long long)m * n.pool.OH * n.pool.OW * 64;
+  each_conv(n, [&](const ConvShape& s) { blk = std::max(blk, out_elems(s)); });
+  // the buffers serve every chunk of up to m rows (a ragged tail, a later
+  // smaller call): the activations grow with the rows, the workspace does not,
+  // so it is the maximum over every row count
+  for (int r = 1; r <= m; ++r) z.ws_floats = std::max(z.ws_floats, ws_floats_at(p, r));
+  z.act[0] = std::max(blk, out_elems(n.stem));
+  z.act[1] = std::max(blk, (long long)m * n.s2d.H * n.s2d.W * 16);
+  z.act[2] = blk;
+  return z;
+}
+
+void ResnetInfer::eval_chunk(const ResnetInferPtrs& p, uintptr_t x, int m, uintptr_t act0,
+                             uintptr_t act1, uintptr_t act2, uintptr_t ws, long long ws_floats,
+                             uintptr_t logits, hipStream_t s) {
+  check(p, m);
+  if (ws_floats < ws_floats_at(p, m))
+    throw std::runtime_error("ResnetInfer: the split-K workspace is smaller than this chunk's "
+                             "plans need (size it with ws_sizes)");
+  if (p.wt.size() != 19 || p.fold_off.size() != 20 || !p.wt8 || !p.fold || !p.fc_w || !p.fc_b ||
+      std::find(p.wt.begin(), p.wt.end(), (uintptr_t)0) != p.wt.end())
+    throw std::runtime_error("ResnetInfer: 19 conv weight copies, the stem filter, 20 fold "
+                             "offsets, the fold table and the FC are required");
+  if (!x || !act0 || !act1 || !act2 || !ws || !logits)
+    throw std::runtime_error("ResnetInfer: null buffer");
+  const Net n(p, m);
+  void* act[3] = {P<void>(act0), P<void>(act1), P<void>(act2)};
+  float* wsf = P<float>(ws);
+  const float* fold = P<const float>(p.fold);
+  gops::s2d_stem_input(P<const float>(x), m, p.H, p.W, n.stem.OH, n.stem.OW, act[1], s);
+  gops::conv_fwd_s2d_stem_affine_bf16(n.s2d, act[1], P<const void>(p.wt8), fold + p.fold_off[0],
+                                      fold + p.fold_total + p.fold_off[0], true, act[0], s);
+  gops::maxpool_infer_b16(n.pool, act[0], act[1], s);
+  int h = 1, t = 0, u = 2;  // the block input, c1's output, the shortcut / the next input
+  size_t wi = 0;
+  int bn = 1;
+  for (const Block& b : n.blocks) {
+    if (b.down) {
+      conv(b.ds, act[h], p.wt[wi + 2], p, bn + 2, nullptr, false, act[u], wsf, s);
+      conv(b.c1, act[h], p.wt[wi], p, bn, nullptr, true, act[t], wsf, s);
+      conv(b.c2, act[t], p.wt[wi + 1], p, bn + 1, act[u], true, act[h], wsf, s);
+      wi += 3, bn += 3;
+    } else {
+      conv(b.c1, act[h], p.wt[wi], p, bn, nullptr, true, act[t], wsf, s);
+      conv(b.c2, act[t], p.wt[wi + 1], p, bn + 1, act[h], true, act[u], wsf, s);
+      std::swap(h, u);
+      wi += 2, bn += 2;
+    }
+  }
+  gops::avgpool_fc(act[h], P<const float>(p.fc_w), P<const float>(p.fc_b), P<float>(logits), m,
+                   n.fh * n.fw, 512, p.classes, s);
+}

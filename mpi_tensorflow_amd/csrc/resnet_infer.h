@@ -1,0 +1,57 @@
+// Native bf16 inference forward of ResNet-18 (models/generic.py ResNet18).
+//
+// Like LenetExecutor::eval_chunk: one static call enqueues the forward of a
+// chunk of rows on a HIP stream, in plain C++ - no allocation, no host
+// synchronisation, one stream, a linear chain of launches (capturable):
+//   s2d_stem_input -> stem conv (bn1 + ReLU in its epilogue) -> max pool
+//   -> 8 BasicBlocks -> avgpool_fc
+// A BasicBlock on input h:
+//   sc = affine(conv_ds(h))            (blocks with a shortcut conv; no ReLU)
+//   t  = relu(affine(conv_c1(h)))
+//   h' = relu(affine(conv_c2(t)) + res),  res = sc or h
+// Every BatchNorm is a folded per-channel (a, b) pair of bn_fold's table,
+// applied in the producing conv's epilogue (conv_fwd_affine_bf16); every
+// activation between two launches is bf16.  Each conv runs the plan
+// plan_fwd_bf16(shape, ConvHave{}) gives - what ops.conv_route reports.
+#pragma once
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+
+#include <vector>
+
+struct ResnetInferPtrs {
+  int H = 224, W = 224;  // input image (3 channels, NHWC fp32)
+  int classes = 10;
+  // bf16 weight operands: the stem's 8x8-extended filter (s2d_stem_weight) and
+  // the forward copies (wcvt_batch mode 0) in forward order - per block c1,
+  // c2, then ds where the block has a shortcut conv (19 in all)
+  uintptr_t wt8 = 0;
+  std::vector<uintptr_t> wt;
+  // bn_fold's table [2][fold_total] and the channel offset of every BatchNorm:
+  // bn1, then per block n1, n2, then nd where it has one (20 in all)
+  uintptr_t fold = 0;
+  int fold_total = 0;
+  std::vector<int> fold_off;
+  uintptr_t fc_w = 0, fc_b = 0;  // fp32 [512][classes], [classes]
+};
+
+struct ResnetInferSizes {
+  // three bf16 activation buffers (elements) and the fp32 split-K workspace (floats)
+  long long act[3] = {0, 0, 0};
+  long long ws_floats = 0;
+};
+
+class ResnetInfer {
+ public:
+  // rows a chunk may hold: the 32-bit pixel x channel offsets of the halo conv
+  // (conv3_ok) and of the pool on the 112 x 112 x 64 stem output
+  static int max_rows(const ResnetInferPtrs& p);
+  // buffers that serve every chunk of 1 .. m rows (the workspace a chunk
+  // needs does not grow with its rows: small chunks split K, large ones do not)
+  static ResnetInferSizes ws_sizes(const ResnetInferPtrs& p, int m);
+  // logits [m][classes] of the m fp32 rows at x; ws holds ws_floats floats,
+  // and a chunk whose plans need more is refused
+  static void eval_chunk(const ResnetInferPtrs& p, uintptr_t x, int m, uintptr_t act0,
+                         uintptr_t act1, uintptr_t act2, uintptr_t ws, long long ws_floats,
+                         uintptr_t logits, hipStream_t s);
+};

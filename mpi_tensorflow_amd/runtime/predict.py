@@ -9,7 +9,10 @@ buffers, no graphs, no extra streams.  On the GPU a chunk of rows goes through
                    augmentation view; csrc/kernels/predict.hip)
     eval_chunk    the engines' own static forward (MnistExecutor /
                    LenetExecutor): the same launches on the same operands as
-                   `engine.evaluate`, so the logits are bit-identical to it
+                   `engine.evaluate`, so the logits are bit-identical to it;
+                   ResNet-18 (bf16): ResnetInfer, the inference forward with
+                   every BatchNorm folded into its conv's epilogue
+                   (docs/ACCURACY.md "ResNet-18 inference forward")
     predict_head  softmax, the mean over the views, scores and top-k
 
 once per view, one head launch per view and chunk.  On the CPU (and with
@@ -39,7 +42,9 @@ from ..parallel import dist as D
 from ..utils import checkpoint as ckpt_mod
 from ..utils.metrics import EvalMetrics
 
-PREDICT_MODELS = ("mnist_cnn", "lenet5")
+PREDICT_MODELS = ("mnist_cnn", "lenet5", "resnet18")
+RESNET_CHUNK = 256  # rows a ResNet-18 chunk holds at most (154 MB of fp32 input)
+BN_EPS = 1e-5  # Fn.batchnorm's default
 
 
 def tta_views(spec: Optional[str], model: str = "mnist_cnn") -> Tuple[List[Tuple[int, int, bool]], float]:
@@ -63,9 +68,6 @@ def input_shape(model: str) -> Tuple[int, int, int]:
 
 
 def _check_model(model: str) -> None:
-    if model == "resnet18":
-        raise ValueError("Predictor does not support resnet18: its forward lives in the autograd "
-                         f"engine; supported models: {PREDICT_MODELS}")
     if model not in PREDICT_MODELS:
         raise ValueError(f"unknown model {model!r}; Predictor supports {PREDICT_MODELS}")
 
@@ -106,11 +108,15 @@ class PredictResult:
 class Predictor:
     def __init__(self, model: str, params: torch.Tensor, dtype: str = "fp32",
                  backend: str = "auto", step: int = 0, meta: Optional[Dict[str, str]] = None,
-                 weights: str = "raw"):
+                 weights: str = "raw",
+                 bn: Optional[Dict[str, Tuple[torch.Tensor, torch.Tensor]]] = None):
         """`params`: the flat fp32 parameter buffer in the model's layout, on
         the device the predictions run on (used in place).  `weights` names
         what it holds: the trained weights ("raw") or their moving average
-        ("ema", --ema); the forward is the same."""
+        ("ema", --ema); the forward is the same.  `bn` (resnet18): every
+        BatchNorm's (running mean, running variance) on the same device, used
+        in place.  resnet18 runs as dtype "bf16" on the native backend or as
+        "fp32" on the torch backend."""
         if weights not in C.PREDICT_WEIGHTS:
             raise ValueError(f"unknown weights {weights!r}; choose from {C.PREDICT_WEIGHTS}")
         self.weights = weights
@@ -126,8 +132,12 @@ class Predictor:
             backend = "native" if self.device.type == "cuda" else "torch"
         if backend == "native" and self.device.type != "cuda":
             raise RuntimeError("the native Predictor needs a GPU")
-        if dtype != "fp32" and (backend != "native" or model != "mnist_cnn"):
-            raise NotImplementedError(f"dtype {dtype} needs the native (GPU) MNIST forward")
+        if model == "resnet18" and backend == "native" and dtype == "fp32":
+            raise ValueError("resnet18: the native inference forward is bf16 (--dtype bf16); fp32 "
+                             "runs on the torch backend only")
+        if dtype != "fp32" and (backend != "native" or model == "lenet5"):
+            raise NotImplementedError(f"dtype {dtype} needs the native (GPU) MNIST or ResNet-18 "
+                                      "forward")
         self.backend = backend
         if params.dtype != torch.float32 or params.dim() != 1 or params.numel() != self.layout.total:
             raise ValueError(f"params must be the flat fp32 buffer of {self.layout.total} floats")
@@ -139,6 +149,18 @@ class Predictor:
         self._ws: Optional[tuple] = None
         self._eval_out: Optional[tuple] = None
         self._shadows = None
+        self.bn = None
+        if model == "resnet18":
+            want = self._generic.bn_channels
+            if bn is None or set(bn) != set(want):
+                raise ValueError("resnet18 needs the BatchNorm statistics `bn` of "
+                                 f"{sorted(want)}")
+            for name, c in want.items():
+                for t in bn[name]:
+                    if t.dtype != torch.float32 or tuple(t.shape) != (c,) or t.device != self.device:
+                        raise ValueError(f"bn[{name!r}] must be two fp32 [{c}] tensors on "
+                                         f"{self.device}")
+            self.bn = {name: (bn[name][0].detach(), bn[name][1].detach()) for name in want}
         if backend == "native":
             self._C = native()
             self.ptrs = self._make_ptrs()
@@ -181,11 +203,24 @@ class Predictor:
                     raise ValueError(f"{path}: {key} ({s.name}) has shape {w.shape}, "
                                      f"expected {s.shape}")
                 views[s.name].copy_(torch.from_numpy(np.ascontiguousarray(w, np.float32)))
+            bn = None
+            if model == "resnet18":  # the names GenericEngine.extra_state saves them under
+                bn = {}
+                for name, c in _layout_of(model)[1].bn_channels.items():
+                    pair = []
+                    for key in (name + "/moving_mean", name + "/moving_variance"):
+                        if key not in z.files:
+                            raise ValueError(f"{path}: missing {key}")
+                        a = z[key]
+                        if tuple(a.shape) != (c,):
+                            raise ValueError(f"{path}: {key} has shape {a.shape}, expected ({c},)")
+                        pair.append(torch.from_numpy(np.ascontiguousarray(a, np.float32)).to(dev))
+                    bn[name] = tuple(pair)
             if ckpt_mod.STEP_META in z.files:
                 step = int(z[ckpt_mod.STEP_META])
             else:
                 step = int(float(z[ckpt_mod.STEP_NAME])) if ckpt_mod.STEP_NAME in z.files else 0
-        return cls(model, host.to(dev), dtype, backend, step, meta, weights)
+        return cls(model, host.to(dev), dtype, backend, step, meta, weights, bn)
 
     @classmethod
     def from_engine(cls, engine, weights: str = "raw") -> "Predictor":
@@ -200,11 +235,19 @@ class Predictor:
                 raise ValueError("the engine keeps no moving average (it was built without --ema)")
         native_kind = str(getattr(engine, "kind", "")).startswith("native")
         dtype = "bf16" if getattr(engine, "bf16", False) and cfg.model == "mnist_cnn" else "fp32"
+        bn = None
+        if cfg.model == "resnet18":  # the engine's own statistics tensors, shared too
+            bn = engine.bn
+            native_kind = bool(engine.bf16 and engine.on_gpu)
+            dtype = "bf16" if native_kind else "fp32"
         return cls(cfg.model, buf, dtype, "native" if native_kind else "torch",
-                   step=getattr(engine, "step", 0), meta={"model": cfg.model}, weights=weights)
+                   step=getattr(engine, "step", 0), meta={"model": cfg.model}, weights=weights,
+                   bn=bn)
 
     def _make_ptrs(self):
         C_, off = self._C, self.layout.offsets
+        if self.model == "resnet18":
+            return self._make_resnet_ptrs()
         if self.model == "lenet5":
             from .lenet_engine import _OFFSETS
 
@@ -232,6 +275,53 @@ class Predictor:
             for name, t in self._shadows.items():
                 setattr(p, name, ptr(t))
         return p
+
+    def _make_resnet_ptrs(self):
+        """The operands of ResnetInfer that are derived from the weights: one
+        buffer of bf16 forward weight copies with its wcvt_batch job table
+        (mode 0 only), the stem's space-to-depth filter, and bn_fold's job
+        table and (a, b) table.  predict() re-derives them all."""
+        C_, dev = self._C, self.device
+        pv = self.layout.views(self.params)
+        convs, folds = [], ["bn1"]
+        for name, cin, c, s, down in self._generic._blocks():
+            convs += [name + "c1_w", name + "c2_w"] + ([name + "ds_w"] if down else [])
+            folds += [name + "n1", name + "n2"] + ([name + "nd"] if down else [])
+        self._wcopy = torch.empty(sum(pv[n].numel() for n in convs), dtype=torch.bfloat16, device=dev)
+        self._wt8 = torch.empty(64 * 256, dtype=torch.bfloat16, device=dev)
+        p = C_.ResnetInferPtrs()
+        p.H, p.W, p.classes = self.shape[0], self.shape[1], self.classes
+        rows, wt, o, blocks = [], [], 0, 0
+        for n in convs:
+            R, S, Ci, K = pv[n].shape
+            out = self._wcopy[o:o + pv[n].numel()]
+            o += pv[n].numel()
+            wt.append(ptr(out))
+            rows.append([ptr(pv[n]), ptr(out), R * S, Ci, K, 0, blocks, 0])
+            blocks += C_.ops.wcvt_blocks(R * S, Ci, K)
+        self._wjobs = torch.tensor(rows, dtype=torch.int64).to(dev)
+        self._wblocks = blocks
+        rows, offs, o = [], [], 0
+        for n in folds:
+            rm, rv = self.bn[n]
+            rows.append([ptr(pv[n + "_g"]), ptr(pv[n + "_b"]), ptr(rm), ptr(rv), rm.numel(), o, 0, 0])
+            offs.append(o)
+            o += rm.numel()
+        self._fjobs = torch.tensor(rows, dtype=torch.int64).to(dev)
+        self._fold = torch.empty(2 * o, dtype=torch.float32, device=dev)
+        p.wt8, p.wt = ptr(self._wt8), wt
+        p.fold, p.fold_total, p.fold_off = ptr(self._fold), o, offs
+        p.fc_w, p.fc_b = ptr(pv["fc_w"]), ptr(pv["fc_b"])
+        return p
+
+    def _derive_resnet(self, s: int) -> None:
+        """The bf16 weight operands and the folded BatchNorms, from the
+        weights and statistics as they are now (three launches)."""
+        ops = self._C.ops
+        ops.wcvt_batch(ptr(self._wjobs), self._wjobs.shape[0], self._wblocks, s)
+        ops.s2d_stem_weight(ptr(self.layout.views(self.params)["conv1_w"]), 64, ptr(self._wt8), s)
+        ops.bn_fold(ptr(self._fjobs), self._fjobs.shape[0], self.ptrs.fold_total, BN_EPS,
+                    ptr(self._fold), s)
 
     # ---------------------------------------------------------------- inputs
     def _rows(self, x) -> torch.Tensor:
@@ -272,6 +362,11 @@ class Predictor:
                   logits=torch.empty(chunk * self.classes, **f32),
                   acc=torch.empty(chunk * self.classes, **f32),
                   y0=torch.zeros(chunk, dtype=torch.int32, device=dev))
+        if self.model == "resnet18":
+            sizes = self._C.ResnetInfer.ws_bytes(self.ptrs, chunk)
+            for i in range(3):
+                ws[f"act{i}"] = torch.empty(sizes[i] // 2, dtype=torch.bfloat16, device=dev)
+            ws["conv_ws"] = torch.empty(max(sizes[3] // 4, 4), **f32)
         if self.model == "mnist_cnn":
             if self.bf16:
                 cp = (chunk + 7) // 8 * 8
@@ -289,7 +384,11 @@ class Predictor:
     def _forward_native(self, x_ptr: int, m: int, ws, s: int) -> None:
         """logits of m fp32 rows at x_ptr into ws['logits'] (the labels are a
         zero buffer and no error counter is passed: nothing is counted here)."""
-        if self.model == "lenet5":
+        if self.model == "resnet18":
+            self._C.ResnetInfer.eval_chunk(self.ptrs, x_ptr, m, ptr(ws["act0"]), ptr(ws["act1"]),
+                                           ptr(ws["act2"]), ptr(ws["conv_ws"]),
+                                           ws["conv_ws"].numel(), ptr(ws["logits"]), s)
+        elif self.model == "lenet5":
             self._C.LenetExecutor.eval_chunk(self.ptrs, x_ptr, ptr(ws["y0"]), m, ptr(ws["logits"]),
                                              0, s)
         else:
@@ -304,7 +403,7 @@ class Predictor:
             return M.forward(self.layout.views(self.params), xb, None)
         pv = self.layout.views(self.params)
         P = {s.name: Fn.Param(pv[s.name], None) for s in self.layout.specs}
-        return self._generic.forward(P, {}, xb, False)
+        return self._generic.forward(P, self.bn or {}, xb, False)
 
     @torch.no_grad()
     def predict(self, x, topk: int = 3, tta: Optional[str] = None, labels=None,
@@ -323,7 +422,7 @@ class Predictor:
         n = int(xd.shape[0])
         yd = self._labels(labels, n)
         dev, Cn = self.device, self.classes
-        chunk = min(int(chunk), max(n, 1))
+        chunk = self._chunk(chunk, n)
         run = self._predict_native if self.backend == "native" else self._predict_torch
         out = Fn.PredictHeadOut(torch.empty((n, Cn), device=dev), torch.empty((n, Cn), device=dev),
                                 torch.empty((n, k), dtype=torch.int32, device=dev),
@@ -362,8 +461,12 @@ class Predictor:
         _, out, mo = self._eval_out
         mo.zero_()
         run = self._predict_native if self.backend == "native" else self._predict_torch
-        run(xd, yd, [(0, 0, False)], 0.0, 1, min(int(chunk), max(n, 1)), out, mo)
+        run(xd, yd, [(0, 0, False)], 0.0, 1, self._chunk(chunk, n), out, mo)
         return mo.result()
+
+    def _chunk(self, chunk: int, n: int) -> int:
+        chunk = min(int(chunk), max(n, 1))
+        return min(chunk, RESNET_CHUNK) if self.model == "resnet18" else chunk
 
     def _sync(self) -> None:
         if self.device.type == "cuda":
@@ -375,7 +478,9 @@ class Predictor:
         row = H * W * Cc
         ws = self._workspace(chunk)
         s = stream_handle()
-        if self.bf16:  # re-derived from the weights as they are now
+        if self.model == "resnet18":
+            self._derive_resnet(s)
+        elif self.bf16:  # re-derived from the weights as they are now
             W_, off = ptr(self.params), self.layout.offsets
             sh = self._shadows
             self._C.mnist.shadows_bf16(W_ + 4 * off["fc1_weight"], W_ + 4 * off["conv2_weight"],
@@ -467,6 +572,11 @@ def _own_split(cfg: C.TrainConfig, split: str, rank: int, world: int):
         return n, rx(a, b), ry(a, b).astype(np.int64), f"{split} ({fx})"
     if split == "val":
         raise ValueError(f"--predict val: the {cfg.model} shards have no validation rows")
+    if cfg.model == "resnet18":  # the trainer's synthetic shard (runtime/trainer.py)
+        per = C.RESNET_SYNTH_ROWS[1]
+        x, y = Dm.synthetic_images_torch(per, input_shape(cfg.model), seed=cfg.seed, split="test",
+                                         start=rank * per)
+        return per * world, x.numpy(), y.numpy().astype(np.int64), f"{split} (synthetic)"
     per = 8192 // 4  # the trainer's synthetic LeNet-5 shard: 8192 train / 2048 test rows a rank
     n = per * world
     x, y = Dm.synthetic_rows("test", rank * per, (rank + 1) * per, cfg.seed, C.NUM_CLASSES,

@@ -156,7 +156,7 @@ class Trainer:
                 self.shard = synthetic_image_shard(self.rank, self.world, rows, rows // 4, shape,
                                                    seed=cfg.seed)
             else:  # 224x224x3: generated with torch (numpy path is too heavy)
-                rows, trows = 512, 256
+                rows, trows = C.RESNET_SYNTH_ROWS
                 tx, ty = synthetic_images_torch(rows, shape, seed=cfg.seed, start=self.rank * rows)
                 sx, sy = synthetic_images_torch(trows, shape, seed=cfg.seed, split="test",
                                                 start=self.rank * trows)
