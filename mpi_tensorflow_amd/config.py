@@ -78,7 +78,9 @@ SYNC_SCHEDULES = ("auto", "buckets", "sharded", "split", "factors", "serial", "d
 COMMS = ("auto", "rccl", "shm", "xgmi", "torch")
 # LeNet-5's sync over the xGMI communicator (TrainConfig.xgmi_mode)
 XGMI_MODES = ("two-phase", "push", "pull")
-DTYPES = ("fp32", "bf16")
+# fp8 (OCP e4m3, post-training): --predict --model resnet18 on the native GPU path only
+DTYPES = ("fp32", "bf16", "fp8")
+PREDICT_CALIB_ROWS = 256  # rows an fp8 predictor calibrates itself on by default
 # --augment: what is shifted in from outside the image unless the spec says
 # fill:V.  MNIST: the normalised raw 0 pixel, (0 - 127.5) / 255; the others:
 # zero-padding of a centred image
@@ -356,6 +358,9 @@ class TrainConfig:
     # raw | ema: the checkpoint's trained weights or their moving average (--ema);
     # None = raw, not named (the JSON record then has no "weights" entry)
     predict_weights: Optional[str] = None
+    # --dtype fp8: leading rows of the source the activation scales are calibrated
+    # on (None = PREDICT_CALIB_ROWS, not named)
+    predict_calib: Optional[int] = None
     quiet: bool = False
     # robustness: process-group / collective timeout (a dead rank turns into
     # an error instead of a hang) and a cross-replica consistency probe at
@@ -417,6 +422,20 @@ class TrainConfig:
             if self.effective_eval_every() == 0:
                 raise ValueError("--ckpt-best needs periodic evaluation (--eval-every > 0)")
             self.eval_metrics = True
+        if self.dtype == "fp8":
+            if self.predict is None:
+                raise ValueError("--dtype fp8 is inference only: it needs --predict SRC (training "
+                                 "runs in fp32 or bf16)")
+            if self.model != "resnet18":
+                raise ValueError(f"--dtype fp8 supports --model resnet18 only, not {self.model}")
+            if self.backend == "torch" or self.device == "cpu":
+                raise ValueError("--dtype fp8 runs on the native GPU forward only: not with "
+                                 "--backend torch or --device cpu")
+        if self.predict_calib is not None:
+            if self.dtype != "fp8":
+                raise ValueError("--predict-calib needs --dtype fp8")
+            if self.predict_calib < 1:
+                raise ValueError(f"--predict-calib must be positive, got {self.predict_calib}")
         if self.predict is not None:
             self._validate_predict()
         elif (self.predict_labels or self.predict_out or self.predict_tta or self.predict_probs):
@@ -585,6 +604,9 @@ def build_arg_parser(prog: str = "mpipy.py") -> argparse.ArgumentParser:
                    help="predict with the checkpoint's trained weights (raw, the default) or with "
                         "their moving average (ema: a checkpoint of an --ema run); when given, "
                         "the JSON record names it under \"weights\"")
+    p.add_argument("--predict-calib", type=int, default=d.predict_calib, metavar="ROWS",
+                   help="--dtype fp8: calibrate the activation scales on the leading ROWS rows "
+                        f"of SRC (default {PREDICT_CALIB_ROWS})")
     p.add_argument("--quiet", action="store_true")
     p.add_argument("--collective-timeout-s", type=float, default=d.collective_timeout_s,
                    help="process-group / collective timeout (seconds)")

@@ -696,6 +696,47 @@ PYBIND11_MODULE(_C, m) {
                      M, HW, C, N, S(st));
     check_launch();
   });
+  // the fp8 (OCP e4m3) inference ops (conv_f8.hip, resnet_infer.hip)
+  g.def("f8conv", [](const gops::ConvShape& s, uintptr_t x8, uintptr_t w8, uintptr_t a2,
+                     uintptr_t b, uintptr_t res, uintptr_t s_res, uintptr_t inv_s_out, bool relu,
+                     uintptr_t y, bool out_bf16, uintptr_t st, int form, int mfma) {
+    const gops::F8Epi e{P<const float>(a2), P<const float>(b), P<const void>(res),
+                        P<const float>(s_res), P<const float>(inv_s_out), relu ? 1 : 0};
+    gops::f8conv(s, P<const void>(x8), P<const void>(w8), e, P<void>(y), out_bf16, form, mfma,
+                 S(st));
+    check_launch();
+  }, py::arg("s"), py::arg("x8"), py::arg("w8"), py::arg("a2"), py::arg("b"), py::arg("res"),
+     py::arg("s_res"), py::arg("inv_s_out"), py::arg("relu"), py::arg("y"), py::arg("out_bf16"),
+     py::arg("st"), py::arg("form") = 0, py::arg("mfma") = 0);
+  // read-only: the tile and loader f8conv runs for a shape ("form": 1 gather, 2 halo)
+  g.def("f8conv_plan", [](const gops::ConvShape& s, int form) {
+    const gops::F8Plan p = gops::f8conv_plan(s, form);
+    py::dict d;
+    d["bm"] = p.bm;
+    d["form"] = p.form;
+    return d;
+  }, py::arg("s"), py::arg("form") = 0);
+  g.def("f8conv_set_mfma", &gops::f8conv_set_mfma);
+  g.def("f8conv_set_form", &gops::f8conv_set_form);
+  g.def("wq_f8", [](uintptr_t jobs, int njobs, long long nblocks, uintptr_t sw, uintptr_t st) {
+    gops::wq_f8(P<const long long>(jobs), njobs, nblocks, P<float>(sw), S(st));
+    check_launch();
+  });
+  g.def("f8_fold", [](uintptr_t jobs, int njobs, uintptr_t fold, uintptr_t sw, uintptr_t amax,
+                      uintptr_t a2, uintptr_t scal, uintptr_t st) {
+    gops::f8_fold(P<const long long>(jobs), njobs, P<const float>(fold), P<const float>(sw),
+                  P<const float>(amax), P<float>(a2), P<float>(scal), S(st));
+    check_launch();
+  });
+  g.def("maxpool_infer_f8", [](const gops::PoolShape& p, uintptr_t xb, uintptr_t inv_s,
+                               uintptr_t y8, uintptr_t st) {
+    gops::maxpool_infer_f8(p, P<const void>(xb), P<const float>(inv_s), P<void>(y8), S(st));
+    check_launch();
+  });
+  g.def("amax_b16", [](uintptr_t xb, long long n, uintptr_t slot, uintptr_t st) {
+    gops::amax_b16(P<const void>(xb), n, P<float>(slot), S(st));
+    check_launch();
+  });
   g.def("conv_ws_floats", &gops::conv_ws_floats);
   g.def("conv_filter_splits", &gops::conv_filter_splits);
   // read-only: the plan the launchers execute for a call (gops::conv_route) -
@@ -1155,7 +1196,12 @@ PYBIND11_MODULE(_C, m) {
       .def_readwrite("fold_total", &ResnetInferPtrs::fold_total)
       .def_readwrite("fold_off", &ResnetInferPtrs::fold_off)
       .def_readwrite("fc_w", &ResnetInferPtrs::fc_w)
-      .def_readwrite("fc_b", &ResnetInferPtrs::fc_b);
+      .def_readwrite("fc_b", &ResnetInferPtrs::fc_b)
+      .def_readwrite("w8", &ResnetInferPtrs::w8)
+      .def_readwrite("amax", &ResnetInferPtrs::amax)
+      .def_readwrite("a2", &ResnetInferPtrs::a2)
+      .def_readwrite("scal", &ResnetInferPtrs::scal)
+      .def_readwrite("calibrated", &ResnetInferPtrs::calibrated);
   py::class_<ResnetInfer>(m, "ResnetInfer")
       .def_static("max_rows", &ResnetInfer::max_rows)
       // bytes of the three bf16 activation buffers and of the fp32 split-K
@@ -1168,6 +1214,19 @@ PYBIND11_MODULE(_C, m) {
                                    uintptr_t act1, uintptr_t act2, uintptr_t ws,
                                    long long ws_floats, uintptr_t logits, uintptr_t s) {
         ResnetInfer::eval_chunk(p, x, rows, act0, act1, act2, ws, ws_floats, logits, S(s));
+        check_launch();
+      })
+      .def_static("calibrate_chunk", [](const ResnetInferPtrs& p, uintptr_t x, int rows,
+                                        uintptr_t act0, uintptr_t act1, uintptr_t act2,
+                                        uintptr_t ws, long long ws_floats, uintptr_t logits,
+                                        uintptr_t s) {
+        ResnetInfer::calibrate_chunk(p, x, rows, act0, act1, act2, ws, ws_floats, logits, S(s));
+        check_launch();
+      })
+      .def_static("eval_chunk_f8", [](const ResnetInferPtrs& p, uintptr_t x, int rows,
+                                      uintptr_t act0, uintptr_t act1, uintptr_t act2,
+                                      uintptr_t logits, uintptr_t s) {
+        ResnetInfer::eval_chunk_f8(p, x, rows, act0, act1, act2, logits, S(s));
         check_launch();
       });
 

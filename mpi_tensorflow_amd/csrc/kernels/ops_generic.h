@@ -214,6 +214,52 @@ void maxpool_infer_b16(const PoolShape& p, const void* xb, void* yb, hipStream_t
 // the pixel sum first (pixel order), times 1 / HW, then the FC; fp32
 void avgpool_fc(const void* xb, const float* w, const float* bias, float* logits, int M, int HW,
                 int C, int N, hipStream_t st);
+// conv_f8.hip: the OCP e4m3 (fp8) inference convs (docs/ACCURACY.md "ResNet-18
+// fp8 inference").  Epilogue of an fp8 conv, fp32, in this order:
+//   v = fmaf(acc, a2[co], b[co]);  v += *s_res * float(res[m][co]) (res e4m3,
+//   optional);  v = max(v, 0) (relu);  y = q(v * *inv_s_out) (e4m3) or bf16(v)
+// q(v) = e4m3_rne(clamp(v, -448, 448)).  s_res and inv_s_out are device floats.
+struct F8Epi {
+  const float* a2 = nullptr;
+  const float* b = nullptr;
+  const void* res = nullptr;  // e4m3 [M][K]
+  const float* s_res = nullptr;
+  const float* inv_s_out = nullptr;
+  int relu = 0;
+};
+struct F8Plan {
+  int bm = 64;   // block rows (x 64 columns)
+  int form = 1;  // 1 the gather loader, 2 the 3x3 / stride 1 halo loader
+};
+// R in {1, 3}, stride in {1, 2}, C % 64 == 0, K % 64 == 0
+bool f8conv_ok(const ConvShape& s);
+// form: 0 the planner's choice, 1 gather, 2 halo (throws where it does not apply)
+F8Plan f8conv_plan(const ConvShape& s, int form);
+// x: e4m3 NHWC; w: e4m3 [tap][k][c] (wq_f8); y: e4m3 or bf16 [M][K].  mfma: 0 the
+// default (f8conv_set_mfma), 1 v_mfma_scale_f32_32x32x64_f8f6f4, 2 four
+// v_mfma_f32_32x32x16_fp8_fp8 a K tile.  No split-K, no atomics.
+void f8conv(const ConvShape& s, const void* x, const void* w, const F8Epi& e, void* y,
+            bool out_bf16, int form, int mfma, hipStream_t st);
+void f8conv_set_mfma(int mf);
+// A/B: the loader form = 0 runs where the halo loader applies (1 gather, 2 halo)
+void f8conv_set_form(int form);
+// every conv's weights quantised in one launch: jobs = device int64 [njobs][8] =
+// {w (HWIO fp32), out (e4m3 [tap][k][c]), taps, C, K, offset into sw, first
+// block, 0}, K / 32 blocks a job, first blocks ascending; sw[offset + k] =
+// scale(max |w[:, :, :, k]|), the codes q(w / sw[k])
+void wq_f8(const long long* jobs, int njobs, long long nblocks, float* sw, hipStream_t st);
+// the per-conv epilogue tables of a net in one launch: jobs = device int64
+// [njobs][8] = {channel offset (bn_fold table, sw, a2), K, amax slot of the
+// input, of the output, of the residual or -1, 0, 0, 0}; a2[off + k] = a[off +
+// k] sw[off + k] s_in; scal[j] = s_res, scal[njobs + j] = 1 / s_out,
+// scal[2 njobs] = 1 / scale(amax[0]) (the pool output); s = scale(amax[slot])
+void f8_fold(const long long* jobs, int njobs, const float* fold, const float* sw,
+             const float* amax, float* a2, float* scal, hipStream_t st);
+// resnet_infer.hip: the bf16 -> e4m3 max pool (C % 16 == 0; inv_s a device
+// float) and max |v| of n bf16 values joined into *slot (atomic max on the bits)
+void maxpool_infer_f8(const PoolShape& p, const void* xb, const float* inv_s, void* y8,
+                      hipStream_t st);
+void amax_b16(const void* xb, long long n, float* slot, hipStream_t st);
 void conv_bwd_filter_bf16(const ConvPlan& p, const float* x, const float* dy, float* ws, float* dw,
                           hipStream_t st, const void* xb, const void* dyb);
 // batched weight re-layout: jobs = device int64 [njobs][8] = {w, out, taps,

@@ -4,6 +4,9 @@
 //                      (a, b) pair, one launch
 //   maxpool_infer_b16  the stem pool, bf16 in / bf16 out, nothing else written
 //   avgpool_fc         the head: global average + FC + bias, one launch
+// and, for the fp8 forward (conv_f8.hip, docs/ACCURACY.md):
+//   maxpool_infer_f8   the stem pool, bf16 in / e4m3 out
+//   amax_b16           max |v| of a bf16 buffer into a slot of the calibration table
 #include <stdexcept>
 
 #include "common.h"
@@ -81,6 +84,82 @@ RINF_KERNEL void maxpool_infer_b16_kernel(PoolShape p, const uint4* __restrict__
   }
 }
 
+// The same pool into e4m3 codes q(max / s_pool) (max commutes with the
+// monotone quantiser): one lane = 16 channels, two 16-byte loads a tap, one
+// 16-byte store.  inv_s: device float, 1 / s_pool (a power of two: exact).
+RINF_KERNEL void maxpool_infer_f8_kernel(PoolShape p, const uint4* __restrict__ x,
+                                         const float* __restrict__ inv_s, uint4* __restrict__ y) {
+  const int C16 = p.C / 16;
+  const int n = p.N * p.OH * p.OW * C16;
+  const float inv = *inv_s;
+  for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < n; i += gridDim.x * blockDim.x) {
+    const int c16 = i % C16;
+    int t = i / C16;
+    const int ox = t % p.OW;
+    t /= p.OW;
+    const int oy = t % p.OH, nn = t / p.OH;
+    float m[16];
+#pragma unroll
+    for (int c = 0; c < 16; ++c) m[c] = -INFINITY;
+    for (int kh = 0; kh < p.k; ++kh) {
+      const int iy = oy * p.stride - p.pad + kh;
+      if (iy < 0 || iy >= p.H) continue;
+      for (int kw = 0; kw < p.k; ++kw) {
+        const int ix = ox * p.stride - p.pad + kw;
+        if (ix < 0 || ix >= p.W) continue;
+        const uint4* src = x + ((size_t)(nn * p.H + iy) * p.W + ix) * (2 * C16) + 2 * c16;
+        const uint4 u = src[0], v = src[1];
+        const uint32_t w[8] = {u.x, u.y, u.z, u.w, v.x, v.y, v.z, v.w};
+#pragma unroll
+        for (int c = 0; c < 8; ++c) {
+          m[2 * c] = fmaxf(m[2 * c], bf_lo(w[c]));
+          m[2 * c + 1] = fmaxf(m[2 * c + 1], bf_hi(w[c]));
+        }
+      }
+    }
+    uint32_t o[4];
+#pragma unroll
+    for (int c = 0; c < 4; ++c) {
+      float q[4];
+#pragma unroll
+      for (int e = 0; e < 4; ++e) q[e] = fminf(fmaxf(m[4 * c + e] * inv, -448.f), 448.f);
+      int pk = __builtin_amdgcn_cvt_pk_fp8_f32(q[0], q[1], 0, false);
+      o[c] = (uint32_t)__builtin_amdgcn_cvt_pk_fp8_f32(q[2], q[3], pk, true);
+    }
+    uint4 ov;
+    ov.x = o[0], ov.y = o[1], ov.z = o[2], ov.w = o[3];
+    y[i] = ov;
+  }
+}
+
+// max |v| over n bf16 values joined into *slot by an atomic max on the bits of
+// the non-negative float (their order is the floats' order; a max does not
+// depend on the order of arrival).  Eight values a 16-byte load, grid-stride;
+// the n % 8 tail by thread 0 of block 0; one atomic a wave.
+RINF_KERNEL void amax_b16_kernel(const uint16_t* __restrict__ x, long long n,
+                                 unsigned* __restrict__ slot) {
+  const long long n8 = n / 8, stride = (long long)gridDim.x * blockDim.x;
+  uint32_t lo = 0, hi = 0;  // bf16 bits with the sign cleared, the halves of a pair apart
+  const uint4* x4 = reinterpret_cast<const uint4*>(x);
+  for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < n8; i += stride) {
+    const uint4 u = x4[i];
+    const uint32_t w[4] = {u.x, u.y, u.z, u.w};
+#pragma unroll
+    for (int c = 0; c < 4; ++c) {
+      lo = max(lo, w[c] & 0x7fffu);
+      hi = max(hi, (w[c] >> 16) & 0x7fffu);
+    }
+  }
+  uint32_t am = lo > hi ? lo : hi;
+  if (blockIdx.x == 0 && threadIdx.x == 0)
+    for (long long i = 8 * n8; i < n; ++i) am = max(am, (uint32_t)x[i] & 0x7fffu);
+  const int lane = threadIdx.x & 63;  // (builtins: the header helpers would be real calls here)
+  for (int m = 32; m >= 1; m >>= 1)
+    am = max(am, (uint32_t)__builtin_amdgcn_ds_bpermute((lane ^ m) << 2, (int)am));
+  if (lane == 0 && am)
+    __hip_atomic_fetch_max(slot, am << 16, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+}
+
 // The head, one workgroup a row.  Phase 1: thread t owns channel pairs t, t +
 // 256, ...: the HW pixels of a pair summed in pixel order in fp32 (one 4-byte
 // load a pixel, a wave reads 256 contiguous bytes), times 1 / HW, into LDS.
@@ -135,6 +214,23 @@ void maxpool_infer_b16(const PoolShape& p, const void* xb, void* yb, hipStream_t
   const long long n = (long long)p.N * p.OH * p.OW * (p.C / 8);
   rinf::maxpool_infer_b16_kernel<<<grid1d(n), 256, 0, st>>>(p, reinterpret_cast<const uint4*>(xb),
                                                             reinterpret_cast<uint4*>(yb));
+}
+
+void maxpool_infer_f8(const PoolShape& p, const void* xb, const float* inv_s, void* y8,
+                      hipStream_t st) {
+  if (p.C % 16 != 0 || p.pad >= p.k || !inv_s || (long long)p.N * p.H * p.W * p.C >= (1LL << 31) ||
+      (long long)p.N * p.OH * p.OW * p.C >= (1LL << 31))
+    throw std::runtime_error("maxpool_infer_f8: unsupported shape");
+  const long long n = (long long)p.N * p.OH * p.OW * (p.C / 16);
+  rinf::maxpool_infer_f8_kernel<<<grid1d(n), 256, 0, st>>>(p, reinterpret_cast<const uint4*>(xb),
+                                                           inv_s, reinterpret_cast<uint4*>(y8));
+}
+
+void amax_b16(const void* xb, long long n, float* slot, hipStream_t st) {
+  if (n < 1 || !xb || !slot) throw std::runtime_error("amax_b16: empty buffer");
+  const long long b = (n / 8 + 255) / 256;
+  rinf::amax_b16_kernel<<<(int)(b < 1 ? 1 : (b > 1024 ? 1024 : b)), 256, 0, st>>>(
+      reinterpret_cast<const uint16_t*>(xb), n, reinterpret_cast<unsigned*>(slot));
 }
 
 void avgpool_fc(const void* xb, const float* w, const float* bias, float* logits, int M, int HW,

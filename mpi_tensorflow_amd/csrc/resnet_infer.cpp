@@ -112,9 +112,10 @@ ResnetInferSizes ResnetInfer::ws_sizes(const ResnetInferPtrs& p, int m) {
   return z;
 }
 
-void ResnetInfer::eval_chunk(const ResnetInferPtrs& p, uintptr_t x, int m, uintptr_t act0,
-                             uintptr_t act1, uintptr_t act2, uintptr_t ws, long long ws_floats,
-                             uintptr_t logits, hipStream_t s) {
+namespace {
+
+void check_bf16(const ResnetInferPtrs& p, int m, uintptr_t x, uintptr_t act0, uintptr_t act1,
+                uintptr_t act2, uintptr_t ws, long long ws_floats, uintptr_t logits) {
   check(p, m);
   if (ws_floats < ws_floats_at(p, m))
     throw std::runtime_error("ResnetInfer: the split-K workspace is smaller than this chunk's "
@@ -125,28 +126,110 @@ void ResnetInfer::eval_chunk(const ResnetInferPtrs& p, uintptr_t x, int m, uintp
                              "offsets, the fold table and the FC are required");
   if (!x || !act0 || !act1 || !act2 || !ws || !logits)
     throw std::runtime_error("ResnetInfer: null buffer");
+}
+
+// the bf16 chain; amax (calibration): max |v| of every tensor the fp8 forward
+// quantises joined into its slot - 0 the pool output, 1 + i the output of conv
+// i (weight order: a block's c1, c2 = the block output, ds)
+void run_bf16(const ResnetInferPtrs& p, uintptr_t x, int m, uintptr_t act0, uintptr_t act1,
+              uintptr_t act2, uintptr_t ws, uintptr_t logits, float* amax, hipStream_t s) {
   const Net n(p, m);
   void* act[3] = {P<void>(act0), P<void>(act1), P<void>(act2)};
   float* wsf = P<float>(ws);
   const float* fold = P<const float>(p.fold);
+  auto seen = [&](const void* t, long long elems, size_t slot) {
+    if (amax) gops::amax_b16(t, elems, amax + slot, s);
+  };
   gops::s2d_stem_input(P<const float>(x), m, p.H, p.W, n.stem.OH, n.stem.OW, act[1], s);
   gops::conv_fwd_s2d_stem_affine_bf16(n.s2d, act[1], P<const void>(p.wt8), fold + p.fold_off[0],
                                       fold + p.fold_total + p.fold_off[0], true, act[0], s);
   gops::maxpool_infer_b16(n.pool, act[0], act[1], s);
+  seen(act[1], (long long)m * n.pool.OH * n.pool.OW * 64, 0);
   int h = 1, t = 0, u = 2;  // the block input, c1's output, the shortcut / the next input
   size_t wi = 0;
   int bn = 1;
   for (const Block& b : n.blocks) {
     if (b.down) {
       conv(b.ds, act[h], p.wt[wi + 2], p, bn + 2, nullptr, false, act[u], wsf, s);
+      seen(act[u], out_elems(b.ds), 1 + wi + 2);
       conv(b.c1, act[h], p.wt[wi], p, bn, nullptr, true, act[t], wsf, s);
+      seen(act[t], out_elems(b.c1), 1 + wi);
       conv(b.c2, act[t], p.wt[wi + 1], p, bn + 1, act[u], true, act[h], wsf, s);
+      seen(act[h], out_elems(b.c2), 1 + wi + 1);
       wi += 3, bn += 3;
     } else {
       conv(b.c1, act[h], p.wt[wi], p, bn, nullptr, true, act[t], wsf, s);
+      seen(act[t], out_elems(b.c1), 1 + wi);
       conv(b.c2, act[t], p.wt[wi + 1], p, bn + 1, act[h], true, act[u], wsf, s);
+      seen(act[u], out_elems(b.c2), 1 + wi + 1);
       std::swap(h, u);
       wi += 2, bn += 2;
+    }
+  }
+  gops::avgpool_fc(act[h], P<const float>(p.fc_w), P<const float>(p.fc_b), P<float>(logits), m,
+                   n.fh * n.fw, 512, p.classes, s);
+}
+
+}  // namespace
+
+void ResnetInfer::eval_chunk(const ResnetInferPtrs& p, uintptr_t x, int m, uintptr_t act0,
+                             uintptr_t act1, uintptr_t act2, uintptr_t ws, long long ws_floats,
+                             uintptr_t logits, hipStream_t s) {
+  check_bf16(p, m, x, act0, act1, act2, ws, ws_floats, logits);
+  run_bf16(p, x, m, act0, act1, act2, ws, logits, nullptr, s);
+}
+
+void ResnetInfer::calibrate_chunk(const ResnetInferPtrs& p, uintptr_t x, int m, uintptr_t act0,
+                                  uintptr_t act1, uintptr_t act2, uintptr_t ws,
+                                  long long ws_floats, uintptr_t logits, hipStream_t s) {
+  check_bf16(p, m, x, act0, act1, act2, ws, ws_floats, logits);
+  if (!p.amax) throw std::runtime_error("ResnetInfer: calibrate_chunk needs the amax table");
+  run_bf16(p, x, m, act0, act1, act2, ws, logits, P<float>(p.amax), s);
+}
+
+void ResnetInfer::eval_chunk_f8(const ResnetInferPtrs& p, uintptr_t x, int m, uintptr_t act0,
+                                uintptr_t act1, uintptr_t act2, uintptr_t logits, hipStream_t s) {
+  check(p, m);
+  if (!p.calibrated)
+    throw std::runtime_error("ResnetInfer: the fp8 forward is not calibrated (calibrate_chunk, "
+                             "then f8_fold)");
+  if (p.w8.size() != 19 || p.fold_off.size() != 20 || !p.wt8 || !p.fold || !p.a2 || !p.scal ||
+      !p.fc_w || !p.fc_b || std::find(p.w8.begin(), p.w8.end(), (uintptr_t)0) != p.w8.end())
+    throw std::runtime_error("ResnetInfer: 19 fp8 weight codes, the stem filter, 20 fold offsets, "
+                             "the fold, a2 and scale tables and the FC are required");
+  if (!x || !act0 || !act1 || !act2 || !logits) throw std::runtime_error("ResnetInfer: null buffer");
+  const Net n(p, m);
+  void* act[3] = {P<void>(act0), P<void>(act1), P<void>(act2)};
+  const float* fold = P<const float>(p.fold);
+  const float* a2 = P<const float>(p.a2);
+  const float* scal = P<const float>(p.scal);
+  gops::s2d_stem_input(P<const float>(x), m, p.H, p.W, n.stem.OH, n.stem.OW, act[1], s);
+  gops::conv_fwd_s2d_stem_affine_bf16(n.s2d, act[1], P<const void>(p.wt8), fold + p.fold_off[0],
+                                      fold + p.fold_total + p.fold_off[0], true, act[0], s);
+  gops::maxpool_infer_f8(n.pool, act[0], scal + 2 * 19, act[1], s);
+  // conv i of the weight order: BatchNorm 1 + i, scales scal[i] / scal[19 + i]
+  auto conv8 = [&](const ConvShape& cs, const void* xin, size_t i, const void* res, bool relu,
+                   void* y, bool last) {
+    gops::F8Epi e;
+    const int off = p.fold_off[1 + i];
+    e.a2 = a2 + off, e.b = fold + p.fold_total + off;
+    e.res = res, e.s_res = scal + i, e.inv_s_out = scal + 19 + i, e.relu = relu ? 1 : 0;
+    gops::f8conv(cs, xin, P<const void>(p.w8[i]), e, y, last, 0, 0, s);
+  };
+  int h = 1, t = 0, u = 2;
+  size_t wi = 0;
+  for (const Block& b : n.blocks) {
+    const bool last = &b == &n.blocks[7];  // the final block output stays bf16 for avgpool_fc
+    if (b.down) {
+      conv8(b.ds, act[h], wi + 2, nullptr, false, act[u], false);
+      conv8(b.c1, act[h], wi, nullptr, true, act[t], false);
+      conv8(b.c2, act[t], wi + 1, act[u], true, act[h], last);
+      wi += 3;
+    } else {
+      conv8(b.c1, act[h], wi, nullptr, true, act[t], false);
+      conv8(b.c2, act[t], wi + 1, act[h], true, act[u], last);
+      std::swap(h, u);
+      wi += 2;
     }
   }
   gops::avgpool_fc(act[h], P<const float>(p.fc_w), P<const float>(p.fc_b), P<float>(logits), m,

@@ -11,7 +11,8 @@
 //   h' = relu(affine(conv_c2(t)) + res),  res = sc or h
 // Every BatchNorm is a folded per-channel (a, b) pair of bn_fold's table,
 // applied in the producing conv's epilogue (conv_fwd_affine_bf16); every
-// activation between two launches is bf16.  Each conv runs the plan
+// activation between two launches is bf16 (eval_chunk) or, behind the max pool
+// of eval_chunk_f8, e4m3 with one calibrated scale a tensor.  Each conv runs the plan
 // plan_fwd_bf16(shape, ConvHave{}) gives - what ops.conv_route reports.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -33,6 +34,14 @@ struct ResnetInferPtrs {
   int fold_total = 0;
   std::vector<int> fold_off;
   uintptr_t fc_w = 0, fc_b = 0;  // fp32 [512][classes], [classes]
+  // the fp8 forward (docs/ACCURACY.md "ResNet-18 fp8 inference"): wq_f8's e4m3
+  // codes [tap][k][c] in the order of wt; amax, the calibration table of 20
+  // floats (slot 0 the pool output, 1 + i the output of conv i); f8_fold's a2
+  // [fold_total] (conv i at fold_off[1 + i]) and scal [2 * 19 + 1] (s_res,
+  // 1 / s_out per conv, 1 / s_pool); calibrated: amax has been filled and folded
+  std::vector<uintptr_t> w8;
+  uintptr_t amax = 0, a2 = 0, scal = 0;
+  bool calibrated = false;
 };
 
 struct ResnetInferSizes {
@@ -54,4 +63,15 @@ class ResnetInfer {
   static void eval_chunk(const ResnetInferPtrs& p, uintptr_t x, int m, uintptr_t act0,
                          uintptr_t act1, uintptr_t act2, uintptr_t ws, long long ws_floats,
                          uintptr_t logits, hipStream_t s);
+  // eval_chunk with an amax_b16 launch behind every tensor the fp8 forward
+  // quantises, joined into p.amax (which accumulates across chunks)
+  static void calibrate_chunk(const ResnetInferPtrs& p, uintptr_t x, int m, uintptr_t act0,
+                              uintptr_t act1, uintptr_t act2, uintptr_t ws, long long ws_floats,
+                              uintptr_t logits, hipStream_t s);
+  // the fp8 forward: the bf16 stem, maxpool_infer_f8, 19 f8conv launches (the
+  // last one writes bf16), avgpool_fc.  The same three buffers (their bytes
+  // suffice), no workspace: no conv splits K, so a row's logits do not depend
+  // on the chunk it arrives in.  Refuses an uncalibrated or incomplete p.
+  static void eval_chunk_f8(const ResnetInferPtrs& p, uintptr_t x, int m, uintptr_t act0,
+                            uintptr_t act1, uintptr_t act2, uintptr_t logits, hipStream_t s);
 };

@@ -12,7 +12,10 @@ buffers, no graphs, no extra streams.  On the GPU a chunk of rows goes through
                    `engine.evaluate`, so the logits are bit-identical to it;
                    ResNet-18 (bf16): ResnetInfer, the inference forward with
                    every BatchNorm folded into its conv's epilogue
-                   (docs/ACCURACY.md "ResNet-18 inference forward")
+                   (docs/ACCURACY.md "ResNet-18 inference forward");
+                   ResNet-18 (fp8): the same chain with the 19 convs behind
+                   the max pool on calibrated e4m3 operands
+                   (docs/ACCURACY.md "ResNet-18 fp8 inference")
     predict_head  softmax, the mean over the views, scores and top-k
 
 once per view, one head launch per view and chunk.  On the CPU (and with
@@ -109,14 +112,17 @@ class Predictor:
     def __init__(self, model: str, params: torch.Tensor, dtype: str = "fp32",
                  backend: str = "auto", step: int = 0, meta: Optional[Dict[str, str]] = None,
                  weights: str = "raw",
-                 bn: Optional[Dict[str, Tuple[torch.Tensor, torch.Tensor]]] = None):
+                 bn: Optional[Dict[str, Tuple[torch.Tensor, torch.Tensor]]] = None,
+                 calib_rows: int = C.PREDICT_CALIB_ROWS):
         """`params`: the flat fp32 parameter buffer in the model's layout, on
         the device the predictions run on (used in place).  `weights` names
         what it holds: the trained weights ("raw") or their moving average
         ("ema", --ema); the forward is the same.  `bn` (resnet18): every
         BatchNorm's (running mean, running variance) on the same device, used
-        in place.  resnet18 runs as dtype "bf16" on the native backend or as
-        "fp32" on the torch backend."""
+        in place.  resnet18 runs as dtype "bf16" or "fp8" on the native backend
+        or as "fp32" on the torch backend.  fp8: the activation scales come from
+        `calibrate`; a predictor that has not been calibrated calibrates itself
+        on the leading min(n, calib_rows) rows of its first input."""
         if weights not in C.PREDICT_WEIGHTS:
             raise ValueError(f"unknown weights {weights!r}; choose from {C.PREDICT_WEIGHTS}")
         self.weights = weights
@@ -135,6 +141,10 @@ class Predictor:
         if model == "resnet18" and backend == "native" and dtype == "fp32":
             raise ValueError("resnet18: the native inference forward is bf16 (--dtype bf16); fp32 "
                              "runs on the torch backend only")
+        if dtype == "fp8" and model != "resnet18":
+            raise ValueError(f"dtype fp8 supports resnet18 only, not {model}")
+        if calib_rows < 1:
+            raise ValueError("calib_rows must be positive")
         if dtype != "fp32" and (backend != "native" or model == "lenet5"):
             raise NotImplementedError(f"dtype {dtype} needs the native (GPU) MNIST or ResNet-18 "
                                       "forward")
@@ -146,6 +156,9 @@ class Predictor:
         self.shape = input_shape(model)
         self.classes = C.NUM_CLASSES
         self.bf16 = dtype == "bf16"
+        self.fp8 = dtype == "fp8"
+        self.calib_rows = int(calib_rows)
+        self.calibrated_on = 0  # rows of the last calibration (fp8)
         self._ws: Optional[tuple] = None
         self._eval_out: Optional[tuple] = None
         self._shadows = None
@@ -169,7 +182,8 @@ class Predictor:
     @classmethod
     def from_checkpoint(cls, path: str, model: Optional[str] = None, dtype: str = "fp32",
                         device: str = "auto", backend: str = "auto",
-                        weights: str = "raw") -> "Predictor":
+                        weights: str = "raw",
+                        calib_rows: int = C.PREDICT_CALIB_ROWS) -> "Predictor":
         """A checkpoint of utils/checkpoint.py, written at any world size (the
         LR schedule and the shards its `world` entry guards do not apply
         here); momentum slots are not read.  weights="ema": the moving
@@ -220,7 +234,7 @@ class Predictor:
                 step = int(z[ckpt_mod.STEP_META])
             else:
                 step = int(float(z[ckpt_mod.STEP_NAME])) if ckpt_mod.STEP_NAME in z.files else 0
-        return cls(model, host.to(dev), dtype, backend, step, meta, weights, bn)
+        return cls(model, host.to(dev), dtype, backend, step, meta, weights, bn, calib_rows)
 
     @classmethod
     def from_engine(cls, engine, weights: str = "raw") -> "Predictor":
@@ -280,27 +294,23 @@ class Predictor:
         """The operands of ResnetInfer that are derived from the weights: one
         buffer of bf16 forward weight copies with its wcvt_batch job table
         (mode 0 only), the stem's space-to-depth filter, and bn_fold's job
-        table and (a, b) table.  predict() re-derives them all."""
+        table and (a, b) table.  predict() re-derives them all.  fp8: wq_f8's
+        codes and scales and f8_fold's tables as well; the bf16 copies are then
+        held only while `calibrate` runs."""
         C_, dev = self._C, self.device
         pv = self.layout.views(self.params)
         convs, folds = [], ["bn1"]
         for name, cin, c, s, down in self._generic._blocks():
             convs += [name + "c1_w", name + "c2_w"] + ([name + "ds_w"] if down else [])
             folds += [name + "n1", name + "n2"] + ([name + "nd"] if down else [])
-        self._wcopy = torch.empty(sum(pv[n].numel() for n in convs), dtype=torch.bfloat16, device=dev)
+        self._convs = convs
+        self._wcopy = None
         self._wt8 = torch.empty(64 * 256, dtype=torch.bfloat16, device=dev)
         p = C_.ResnetInferPtrs()
         p.H, p.W, p.classes = self.shape[0], self.shape[1], self.classes
-        rows, wt, o, blocks = [], [], 0, 0
-        for n in convs:
-            R, S, Ci, K = pv[n].shape
-            out = self._wcopy[o:o + pv[n].numel()]
-            o += pv[n].numel()
-            wt.append(ptr(out))
-            rows.append([ptr(pv[n]), ptr(out), R * S, Ci, K, 0, blocks, 0])
-            blocks += C_.ops.wcvt_blocks(R * S, Ci, K)
-        self._wjobs = torch.tensor(rows, dtype=torch.int64).to(dev)
-        self._wblocks = blocks
+        self.ptrs = p
+        if not self.fp8:
+            self._hold_bf16_copies(True)
         rows, offs, o = [], [], 0
         for n in folds:
             rm, rv = self.bn[n]
@@ -309,19 +319,117 @@ class Predictor:
             o += rm.numel()
         self._fjobs = torch.tensor(rows, dtype=torch.int64).to(dev)
         self._fold = torch.empty(2 * o, dtype=torch.float32, device=dev)
-        p.wt8, p.wt = ptr(self._wt8), wt
+        p.wt8 = ptr(self._wt8)
         p.fold, p.fold_total, p.fold_off = ptr(self._fold), o, offs
         p.fc_w, p.fc_b = ptr(pv["fc_w"]), ptr(pv["fc_b"])
+        if self.fp8:
+            self._make_fp8_tables(pv, convs, offs, o)
         return p
+
+    def _hold_bf16_copies(self, on: bool) -> None:
+        """Allocates (or drops) the bf16 forward weight copies and their job table."""
+        p, dev = self.ptrs, self.device
+        if not on:
+            self._wcopy, self._wjobs, p.wt = None, None, []
+            return
+        pv = self.layout.views(self.params)
+        self._wcopy = torch.empty(sum(pv[n].numel() for n in self._convs), dtype=torch.bfloat16,
+                                  device=dev)
+        rows, wt, o, blocks = [], [], 0, 0
+        for n in self._convs:
+            R, S, Ci, K = pv[n].shape
+            out = self._wcopy[o:o + pv[n].numel()]
+            o += pv[n].numel()
+            wt.append(ptr(out))
+            rows.append([ptr(pv[n]), ptr(out), R * S, Ci, K, 0, blocks, 0])
+            blocks += self._C.ops.wcvt_blocks(R * S, Ci, K)
+        self._wjobs = torch.tensor(rows, dtype=torch.int64).to(dev)
+        self._wblocks = blocks
+        p.wt = wt
+
+    def _make_fp8_tables(self, pv, convs, offs, total) -> None:
+        """wq_f8's job table, codes and scales; the calibration table (slot 0
+        the pool output, 1 + i the output of conv i); f8_fold's job table (which
+        tensor each conv reads, writes and adds) and its outputs."""
+        p, dev = self.ptrs, self.device
+        f32 = dict(dtype=torch.float32, device=dev)
+        self._w8 = torch.empty(sum(pv[n].numel() for n in convs), dtype=torch.uint8, device=dev)
+        self._sw, self._a2 = torch.empty(total, **f32), torch.empty(total, **f32)
+        self._amax, self._scal = torch.zeros(len(convs) + 1, **f32), torch.empty(2 * len(convs) + 1, **f32)
+        rows, w8, o, blocks = [], [], 0, 0
+        for i, n in enumerate(convs):
+            R, S, Ci, K = pv[n].shape
+            out = self._w8[o:o + pv[n].numel()]
+            o += pv[n].numel()
+            w8.append(ptr(out))
+            rows.append([ptr(pv[n]), ptr(out), R * S, Ci, K, offs[1 + i], blocks, 0])
+            blocks += K // 32
+        self._qjobs, self._qblocks = torch.tensor(rows, dtype=torch.int64).to(dev), blocks
+        rows, i, src = [], 0, 0  # src: the slot of the block input
+        for name, cin, c, s, down in self._generic._blocks():
+            res = 1 + i + 2 if down else src
+            rows.append([offs[1 + i], c, src, 1 + i, -1, 0, 0, 0])  # c1
+            rows.append([offs[2 + i], c, 1 + i, 2 + i, res, 0, 0, 0])  # c2 -> the block output
+            if down:
+                rows.append([offs[3 + i], c, src, 3 + i, -1, 0, 0, 0])  # ds
+            src, i = 2 + i, i + (3 if down else 2)
+        self._f8jobs = torch.tensor(rows, dtype=torch.int64).to(dev)
+        p.w8, p.amax, p.a2, p.scal = w8, ptr(self._amax), ptr(self._a2), ptr(self._scal)
 
     def _derive_resnet(self, s: int) -> None:
         """The bf16 weight operands and the folded BatchNorms, from the
         weights and statistics as they are now (three launches)."""
         ops = self._C.ops
-        ops.wcvt_batch(ptr(self._wjobs), self._wjobs.shape[0], self._wblocks, s)
+        if self._wcopy is not None:
+            ops.wcvt_batch(ptr(self._wjobs), self._wjobs.shape[0], self._wblocks, s)
         ops.s2d_stem_weight(ptr(self.layout.views(self.params)["conv1_w"]), 64, ptr(self._wt8), s)
         ops.bn_fold(ptr(self._fjobs), self._fjobs.shape[0], self.ptrs.fold_total, BN_EPS,
                     ptr(self._fold), s)
+        if self.fp8:
+            ops.wq_f8(ptr(self._qjobs), self._qjobs.shape[0], self._qblocks, ptr(self._sw), s)
+            if self.ptrs.calibrated:
+                self._f8_fold(s)
+
+    def _f8_fold(self, s: int) -> None:
+        self._C.ops.f8_fold(ptr(self._f8jobs), self._f8jobs.shape[0], ptr(self._fold),
+                            ptr(self._sw), ptr(self._amax), ptr(self._a2), ptr(self._scal), s)
+
+    @torch.no_grad()
+    def calibrate(self, x, chunk: int = RESNET_CHUNK) -> int:
+        """fp8: the activation scales from the rows x.  Zeroes the amax table,
+        runs the bf16 forward over x with a max |value| launch behind every
+        tensor the fp8 forward quantises (calibrate_chunk), and folds.  The
+        scales stay until the next call.  -> the rows used."""
+        if not self.fp8:
+            raise ValueError("calibrate: only a dtype fp8 predictor has scales to calibrate")
+        xd = self._rows(x)
+        n = int(xd.shape[0])
+        if n < 1 or chunk < 1:
+            raise ValueError("calibrate needs at least one row and a positive chunk")
+        chunk = self._chunk(chunk, n)
+        ws, s, p = self._workspace(chunk), stream_handle(), self.ptrs
+        row = int(np.prod(self.shape))
+        self._hold_bf16_copies(True)
+        try:
+            p.calibrated = False
+            self._amax.zero_()
+            self._derive_resnet(s)
+            for a in range(0, n, chunk):
+                m = min(chunk, n - a)
+                if xd.dtype == torch.float32:
+                    x_ptr = ptr(xd) + 4 * row * a
+                else:
+                    Fn.predict_prep(xd[a:a + m], 0, 0, False, 0.0, out=ws["xv"])
+                    x_ptr = ptr(ws["xv"])
+                self._C.ResnetInfer.calibrate_chunk(p, x_ptr, m, ptr(ws["act0"]), ptr(ws["act1"]),
+                                                    ptr(ws["act2"]), ptr(ws["conv_ws"]),
+                                                    ws["conv_ws"].numel(), ptr(ws["logits"]), s)
+            self._f8_fold(s)
+            self._sync()  # the copies are dropped below: their readers have finished
+        finally:
+            self._hold_bf16_copies(False)
+        p.calibrated, self.calibrated_on = True, n
+        return n
 
     # ---------------------------------------------------------------- inputs
     def _rows(self, x) -> torch.Tensor:
@@ -384,7 +492,10 @@ class Predictor:
     def _forward_native(self, x_ptr: int, m: int, ws, s: int) -> None:
         """logits of m fp32 rows at x_ptr into ws['logits'] (the labels are a
         zero buffer and no error counter is passed: nothing is counted here)."""
-        if self.model == "resnet18":
+        if self.fp8:
+            self._C.ResnetInfer.eval_chunk_f8(self.ptrs, x_ptr, m, ptr(ws["act0"]), ptr(ws["act1"]),
+                                              ptr(ws["act2"]), ptr(ws["logits"]), s)
+        elif self.model == "resnet18":
             self._C.ResnetInfer.eval_chunk(self.ptrs, x_ptr, m, ptr(ws["act0"]), ptr(ws["act1"]),
                                            ptr(ws["act2"]), ptr(ws["conv_ws"]),
                                            ws["conv_ws"].numel(), ptr(ws["logits"]), s)
@@ -478,6 +589,8 @@ class Predictor:
         row = H * W * Cc
         ws = self._workspace(chunk)
         s = stream_handle()
+        if self.fp8 and not self.ptrs.calibrated:
+            self.calibrate(xd[:min(int(xd.shape[0]), self.calib_rows)], chunk)
         if self.model == "resnet18":
             self._derive_resnet(s)
         elif self.bf16:  # re-derived from the weights as they are now
@@ -616,7 +729,8 @@ def predict_main(cfg: C.TrainConfig, di: Optional[D.DistInfo] = None) -> Dict:
     di = di or D.init(str(device), timeout_s=cfg.collective_timeout_s)
     rank, world = di.rank, di.world
     pr = Predictor.from_checkpoint(cfg.resume, model=cfg.model, dtype=cfg.dtype, device=device,
-                                   backend=cfg.backend, weights=cfg.predict_weights or "raw")
+                                   backend=cfg.backend, weights=cfg.predict_weights or "raw",
+                                   calib_rows=cfg.predict_calib or C.PREDICT_CALIB_ROWS)
     n, a, x, y, desc = load_source(cfg, rank, world)
     views = len(tta_views(cfg.predict_tta, cfg.model)[0])
     res = pr.predict(x, topk=cfg.predict_topk, tta=cfg.predict_tta, labels=y,
@@ -638,6 +752,8 @@ def predict_main(cfg: C.TrainConfig, di: Optional[D.DistInfo] = None) -> Dict:
     rec = {"model": pr.model, "dtype": pr.dtype, "n": n, "views": views, "world": world,
            "checkpoint_step": pr.step, "images_per_sec": n / max(seconds, 1e-9),
            "out": cfg.predict_out}
+    if pr.fp8:  # the rows this rank's activation scales were calibrated on
+        rec["calib_rows"] = pr.calibrated_on
     if cfg.predict_weights is not None:  # (a record without the flag is what it always was)
         rec["weights"] = pr.weights
     if metrics is not None:

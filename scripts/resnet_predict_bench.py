@@ -3,6 +3,12 @@ against GenericEngine.evaluate on the same weights, rows and device, in one
 process, the two alternating (docs/PERF_NOTES.md holds a run's figures).
 
     python scripts/resnet_predict_bench.py [--rows 1000] [--chunk 256] [--reps 25] [--windows 5]
+                                           [--dtype bf16|fp8]
+
+--dtype fp8: the bf16 Predictor against an fp8 one on the same weights
+(calibrated on the leading 256 rows), and with it the fp8 A/Bs - the MFMA form
+(32x32x16 fp8_fp8 / 32x32x64 f8f6f4) and the loader of the 3x3 stride-1 convs
+(gather / halo) - all alternating in the one process.
 
 A window is `reps` passes over the `rows` device-resident fp32 rows between two
 synchronisations (a few hundred ms); the first window of each path is the
@@ -32,6 +38,7 @@ def main():
     ap.add_argument("--chunk", type=int, default=256)
     ap.add_argument("--reps", type=int, default=25)
     ap.add_argument("--windows", type=int, default=5)
+    ap.add_argument("--dtype", default="bf16", choices=("bf16", "fp8"))
     a = ap.parse_args()
     assert torch.cuda.is_available(), "needs a GPU"
     dev = torch.device("cuda:0")
@@ -57,6 +64,22 @@ def main():
 
     paths = {"evaluate": lambda: eng.evaluate(x, y, chunk=a.chunk),  # (x stays cached on the device)
              "predict": lambda: pr.predict(xd, chunk=a.chunk)}
+    if a.dtype == "fp8":
+        from mpi_tensorflow_amd.ops import native
+
+        ops = native().ops
+        pr8 = Predictor("resnet18", eng.params, dtype="fp8", bn=eng.bn)
+        pr8.calibrate(xd[:256], chunk=a.chunk)
+
+        def fp8(mfma, form):
+            def run():
+                ops.f8conv_set_mfma(mfma)
+                ops.f8conv_set_form(form)
+                pr8.predict(xd, chunk=a.chunk)
+            return run
+
+        paths = {"predict": paths["predict"], "fp8_x16_gather": fp8(2, 1), "fp8_x64_gather": fp8(1, 1),
+                 "fp8_x16_halo": fp8(2, 2), "fp8_x64_halo": fp8(1, 2)}
     rate = {k: [] for k in paths}
     for _ in range(a.windows + 1):
         for k, fn in paths.items():
@@ -65,7 +88,11 @@ def main():
     for k, v in rate.items():
         v = v[1:]
         rec[k + "_img_s"] = {"min": round(min(v)), "median": round(statistics.median(v)), "max": round(max(v))}
-    rec["ratio_of_medians"] = round(rec["predict_img_s"]["median"] / rec["evaluate_img_s"]["median"], 3)
+    base = "evaluate" if a.dtype == "bf16" else "predict"
+    for k in rate:
+        if k != base and (a.dtype == "fp8" or k == "predict"):
+            name = "ratio_of_medians" if a.dtype == "bf16" else k + "_over_bf16"
+            rec[name] = round(rec[k + "_img_s"]["median"] / rec[base + "_img_s"]["median"], 3)
     print(json.dumps(rec))
 
 
