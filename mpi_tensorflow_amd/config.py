@@ -79,7 +79,9 @@ COMMS = ("auto", "rccl", "shm", "xgmi", "torch")
 # LeNet-5's sync over the xGMI communicator (TrainConfig.xgmi_mode)
 XGMI_MODES = ("two-phase", "push", "pull")
 # fp8 (OCP e4m3, post-training): --predict --model resnet18 on the native GPU path only
-DTYPES = ("fp32", "bf16", "fp8")
+# bf16x3 (every fp32 value as a bf16 hi + lo pair, three bf16 MFMA products a
+# multiply: fp32-class results): the same path and restrictions as fp8
+DTYPES = ("fp32", "bf16", "fp8", "bf16x3")
 PREDICT_CALIB_ROWS = 256  # rows an fp8 predictor calibrates itself on by default
 # --augment: what is shifted in from outside the image unless the spec says
 # fill:V.  MNIST: the normalised raw 0 pixel, (0 - 127.5) / 255; the others:
@@ -431,6 +433,15 @@ class TrainConfig:
             if self.backend == "torch" or self.device == "cpu":
                 raise ValueError("--dtype fp8 runs on the native GPU forward only: not with "
                                  "--backend torch or --device cpu")
+        if self.dtype == "bf16x3":
+            if self.predict is None:
+                raise ValueError("--dtype bf16x3 is inference only: it needs --predict SRC "
+                                 "(training runs in fp32 or bf16)")
+            if self.model != "resnet18":
+                raise ValueError(f"--dtype bf16x3 supports --model resnet18 only, not {self.model}")
+            if self.backend == "torch" or self.device == "cpu":
+                raise ValueError("--dtype bf16x3 runs on the native GPU forward only: not with "
+                                 "--backend torch or --device cpu")
         if self.predict_calib is not None:
             if self.dtype != "fp8":
                 raise ValueError("--predict-calib needs --dtype fp8")
@@ -455,7 +466,7 @@ class TrainConfig:
                 and self.device != "cpu"):
             raise ValueError("--predict --model resnet18: the native inference forward is bf16, "
                              "pass --dtype bf16 (fp32 runs on the torch path only: --backend "
-                             "torch or --device cpu)")
+                             "torch or --device cpu), or --dtype bf16x3 for fp32-class results")
         if not 1 <= self.predict_topk <= NUM_CLASSES:
             raise ValueError(f"--predict-topk must be in [1, {NUM_CLASSES}], got "
                              f"{self.predict_topk}")

@@ -733,6 +733,57 @@ PYBIND11_MODULE(_C, m) {
     gops::maxpool_infer_f8(p, P<const void>(xb), P<const float>(inv_s), P<void>(y8), S(st));
     check_launch();
   });
+  // the bf16x3 (split-operand bf16) inference ops (conv_x3.hip, resnet_infer.hip)
+  g.def("x3conv", [](const gops::ConvShape& s, uintptr_t x, uintptr_t w, uintptr_t a, uintptr_t b,
+                     uintptr_t res, bool relu, uintptr_t y, uintptr_t st, int form) {
+    const gops::X3Epi e{P<const float>(a), P<const float>(b), P<const void>(res), relu ? 1 : 0};
+    gops::x3conv(s, P<const void>(x), P<const void>(w), e, P<void>(y), form, S(st));
+    check_launch();
+  }, py::arg("s"), py::arg("x"), py::arg("w"), py::arg("a"), py::arg("b"), py::arg("res"),
+     py::arg("relu"), py::arg("y"), py::arg("st"), py::arg("form") = 0);
+  // read-only: the loader and tile x3conv runs for a shape, in conv_route's terms
+  g.def("x3conv_route", [](const gops::ConvShape& s, int form) {
+    const gops::X3Plan p = gops::x3conv_plan(s, form);
+    py::dict d;
+    d["family"] = std::string("bf16x3");
+    d["kernel"] = std::string("x3conv_kernel");
+    d["loader"] = std::string(p.form == 3 ? "stem" : p.form == 2 ? "halo" : "gather");
+    d["bm"] = p.bm;
+    d["bn"] = 64;
+    d["bk"] = 32;
+    d["z"] = 1;
+    d["halo"] = p.form == 2;
+    d["stem"] = p.form == 3;
+    d["ws_floats"] = 0;
+    return d;
+  }, py::arg("s"), py::arg("form") = 0);
+  g.def("x3_split", [](uintptr_t x, long long n, uintptr_t planes, uintptr_t st) {
+    gops::x3_split(P<const float>(x), n, P<void>(planes), S(st));
+    check_launch();
+  });
+  g.def("wsplit_x3", [](uintptr_t jobs, int njobs, long long nblocks, uintptr_t st) {
+    gops::wsplit_x3(P<const long long>(jobs), njobs, nblocks, S(st));
+    check_launch();
+  });
+  g.def("s2d_stem_input_x3", [](uintptr_t x, int N, int H, int W, int OH, int OW, uintptr_t xs,
+                                uintptr_t st) {
+    gops::s2d_stem_input_x3(P<const float>(x), N, H, W, OH, OW, P<void>(xs), S(st));
+    check_launch();
+  });
+  g.def("s2d_stem_weight_x3", [](uintptr_t w, int K, uintptr_t wt8, uintptr_t st) {
+    gops::s2d_stem_weight_x3(P<const float>(w), K, P<void>(wt8), S(st));
+    check_launch();
+  });
+  g.def("maxpool_infer_x3", [](const gops::PoolShape& p, uintptr_t x, uintptr_t y, uintptr_t st) {
+    gops::maxpool_infer_x3(p, P<const void>(x), P<void>(y), S(st));
+    check_launch();
+  });
+  g.def("avgpool_fc_x3", [](uintptr_t x, uintptr_t w, uintptr_t bias, uintptr_t logits, int M,
+                            int HW, int C, int N, uintptr_t st) {
+    gops::avgpool_fc_x3(P<const void>(x), P<const float>(w), P<const float>(bias),
+                        P<float>(logits), M, HW, C, N, S(st));
+    check_launch();
+  });
   g.def("amax_b16", [](uintptr_t xb, long long n, uintptr_t slot, uintptr_t st) {
     gops::amax_b16(P<const void>(xb), n, P<float>(slot), S(st));
     check_launch();
@@ -1201,14 +1252,18 @@ PYBIND11_MODULE(_C, m) {
       .def_readwrite("amax", &ResnetInferPtrs::amax)
       .def_readwrite("a2", &ResnetInferPtrs::a2)
       .def_readwrite("scal", &ResnetInferPtrs::scal)
-      .def_readwrite("calibrated", &ResnetInferPtrs::calibrated);
+      .def_readwrite("calibrated", &ResnetInferPtrs::calibrated)
+      .def_readwrite("wt8x3", &ResnetInferPtrs::wt8x3)
+      .def_readwrite("wx3", &ResnetInferPtrs::wx3)
+      .def_readwrite("x3", &ResnetInferPtrs::x3);
   py::class_<ResnetInfer>(m, "ResnetInfer")
       .def_static("max_rows", &ResnetInfer::max_rows)
-      // bytes of the three bf16 activation buffers and of the fp32 split-K
-      // workspace that serve every chunk of up to `rows` rows
+      // bytes of the three activation buffers (bf16; p.x3: bf16x3 pairs) and of
+      // the fp32 split-K workspace that serve every chunk of up to `rows` rows
       .def_static("ws_bytes", [](const ResnetInferPtrs& p, int rows) {
         const ResnetInferSizes z = ResnetInfer::ws_sizes(p, rows);
-        return py::make_tuple(2 * z.act[0], 2 * z.act[1], 2 * z.act[2], 4 * z.ws_floats);
+        const long long b = z.act_bytes;
+        return py::make_tuple(b * z.act[0], b * z.act[1], b * z.act[2], 4 * z.ws_floats);
       })
       .def_static("eval_chunk", [](const ResnetInferPtrs& p, uintptr_t x, int rows, uintptr_t act0,
                                    uintptr_t act1, uintptr_t act2, uintptr_t ws,
@@ -1227,6 +1282,12 @@ PYBIND11_MODULE(_C, m) {
                                       uintptr_t act0, uintptr_t act1, uintptr_t act2,
                                       uintptr_t logits, uintptr_t s) {
         ResnetInfer::eval_chunk_f8(p, x, rows, act0, act1, act2, logits, S(s));
+        check_launch();
+      })
+      .def_static("eval_chunk_x3", [](const ResnetInferPtrs& p, uintptr_t x, int rows,
+                                      uintptr_t act0, uintptr_t act1, uintptr_t act2,
+                                      uintptr_t logits, uintptr_t s) {
+        ResnetInfer::eval_chunk_x3(p, x, rows, act0, act1, act2, logits, S(s));
         check_launch();
       });
 

@@ -260,6 +260,48 @@ void f8_fold(const long long* jobs, int njobs, const float* fold, const float* s
 void maxpool_infer_f8(const PoolShape& p, const void* xb, const float* inv_s, void* y8,
                       hipStream_t st);
 void amax_b16(const void* xb, long long n, float* slot, hipStream_t st);
+// conv_x3.hip: the split-operand bf16 ("bf16x3") inference convs (docs/ACCURACY.md
+// "ResNet-18 bf16x3 inference").  A split tensor is two bf16 planes of the
+// tensor's shape, hi = bf16_rne(v) then lo = bf16_rne(v - hi), numel elements
+// apart in one buffer.  Epilogue of an x3 conv, fp32, in this order:
+//   v = fmaf(acc, a[co], b[co]);  v += hi + lo of res[m][co] (a split [M][K],
+//   optional);  v = max(v, 0) (relu);  y = split(v)
+struct X3Epi {
+  const float* a = nullptr;
+  const float* b = nullptr;
+  const void* res = nullptr;
+  int relu = 0;
+};
+struct X3Plan {
+  int bm = 64;   // block rows (x 64 columns)
+  int form = 1;  // 1 the gather loader, 2 the 3x3 / stride 1 halo loader, 3 the s2d stem
+};
+// R in {1, 3}, stride in {1, 2}, C % 32 == 0, K % 64 == 0; or the stem's 4x4 /
+// stride 1 / pad 0 conv over the 16-channel space-to-depth image
+bool x3conv_ok(const ConvShape& s);
+// form: 0 the planner's choice, 1 gather, 2 halo, 3 stem (throws where it does not apply)
+X3Plan x3conv_plan(const ConvShape& s, int form);
+// x: split NHWC; w: split [tap][k][c] (wsplit_x3) or, stem, [k][256]
+// (s2d_stem_weight_x3); y: split [M][K].  acc = sum of xh wh + xh wl + xl wh on
+// v_mfma_f32_32x32x16_bf16, fp32, one fixed order: no split-K, no atomics.
+void x3conv(const ConvShape& s, const void* x, const void* w, const X3Epi& e, void* y, int form,
+            hipStream_t st);
+// n fp32 values -> planes [2][n]
+void x3_split(const float* x, long long n, void* planes, hipStream_t st);
+// every conv's weights split in one launch: jobs = device int64 [njobs][8] = {w
+// (HWIO fp32), out (planes [2][tap][k][c]), taps, C, K, 0, first block, 0}, K /
+// 32 blocks a job, first blocks ascending; C % 32 == 0, K % 32 == 0
+void wsplit_x3(const long long* jobs, int njobs, long long nblocks, hipStream_t st);
+// the split forms of s2d_stem_input / s2d_stem_weight: xs planes [2][N][OH + 3][OW
+// + 3][16], wt8 planes [2][K][256]
+void s2d_stem_input_x3(const float* x, int N, int H, int W, int OH, int OW, void* xs,
+                       hipStream_t st);
+void s2d_stem_weight_x3(const float* w, int K, void* wt8, hipStream_t st);
+// resnet_infer.hip: the max pool of a split tensor (it compares hi + lo and
+// keeps the winning pair; C % 8 == 0) and the head on a split [M][HW][C]
+void maxpool_infer_x3(const PoolShape& p, const void* x, void* y, hipStream_t st);
+void avgpool_fc_x3(const void* x, const float* w, const float* bias, float* logits, int M, int HW,
+                   int C, int N, hipStream_t st);
 void conv_bwd_filter_bf16(const ConvPlan& p, const float* x, const float* dy, float* ws, float* dw,
                           hipStream_t st, const void* xb, const void* dyb);
 // batched weight re-layout: jobs = device int64 [njobs][8] = {w, out, taps,

@@ -7,6 +7,9 @@
 // and, for the fp8 forward (conv_f8.hip, docs/ACCURACY.md):
 //   maxpool_infer_f8   the stem pool, bf16 in / e4m3 out
 //   amax_b16           max |v| of a bf16 buffer into a slot of the calibration table
+// and, for the bf16x3 forward (conv_x3.hip), on split tensors (two bf16 planes):
+//   maxpool_infer_x3   the stem pool: compares hi + lo, keeps the winning pair
+//   avgpool_fc<true>   the head on hi + lo
 #include <stdexcept>
 
 #include "common.h"
@@ -132,6 +135,54 @@ RINF_KERNEL void maxpool_infer_f8_kernel(PoolShape p, const uint4* __restrict__ 
   }
 }
 
+// The pool of a split tensor (planes numel apart): one lane = 8 channels of one
+// output pixel, a 16-byte load per plane and tap; the taps are compared by
+// their joined value hi + lo (exact in fp32) and the FIRST greatest tap's pair
+// is stored unchanged.
+RINF_KERNEL void maxpool_infer_x3_kernel(PoolShape p, const uint4* __restrict__ x,
+                                         uint4* __restrict__ y) {
+  const int C8 = p.C / 8;
+  const int n = p.N * p.OH * p.OW * C8;
+  const size_t xl = (size_t)p.N * p.H * p.W * C8;  // the lo planes, in uint4
+  for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < n; i += gridDim.x * blockDim.x) {
+    const int c8 = i % C8;
+    int t = i / C8;
+    const int ox = t % p.OW;
+    t /= p.OW;
+    const int oy = t % p.OH, nn = t / p.OH;
+    float m[8];
+    uint32_t bh[8], bl[8];  // the winner's bf16 bits
+#pragma unroll
+    for (int c = 0; c < 8; ++c) m[c] = -INFINITY, bh[c] = 0xff80u, bl[c] = 0u;
+    for (int kh = 0; kh < p.k; ++kh) {
+      const int iy = oy * p.stride - p.pad + kh;
+      if (iy < 0 || iy >= p.H) continue;
+      for (int kw = 0; kw < p.k; ++kw) {
+        const int ix = ox * p.stride - p.pad + kw;
+        if (ix < 0 || ix >= p.W) continue;
+        const size_t at = (size_t)((nn * p.H + iy) * p.W + ix) * C8 + c8;
+        const uint4 u = x[at], v = x[xl + at];
+        const uint32_t wh[4] = {u.x, u.y, u.z, u.w}, wl[4] = {v.x, v.y, v.z, v.w};
+#pragma unroll
+        for (int c = 0; c < 8; ++c) {
+          const uint32_t hb = c & 1 ? wh[c / 2] >> 16 : wh[c / 2] & 0xffffu;
+          const uint32_t lb = c & 1 ? wl[c / 2] >> 16 : wl[c / 2] & 0xffffu;
+          const float j = __uint_as_float(hb << 16) + __uint_as_float(lb << 16);
+          const bool win = j > m[c];
+          m[c] = win ? j : m[c], bh[c] = win ? hb : bh[c], bl[c] = win ? lb : bl[c];
+        }
+      }
+    }
+    uint4 oh, ol;
+    oh.x = bh[0] | bh[1] << 16, oh.y = bh[2] | bh[3] << 16, oh.z = bh[4] | bh[5] << 16,
+    oh.w = bh[6] | bh[7] << 16;
+    ol.x = bl[0] | bl[1] << 16, ol.y = bl[2] | bl[3] << 16, ol.z = bl[4] | bl[5] << 16,
+    ol.w = bl[6] | bl[7] << 16;
+    y[i] = oh;
+    y[(size_t)n + i] = ol;
+  }
+}
+
 // max |v| over n bf16 values joined into *slot by an atomic max on the bits of
 // the non-negative float (their order is the floats' order; a max does not
 // depend on the order of arrival).  Eight values a 16-byte load, grid-stride;
@@ -165,11 +216,13 @@ RINF_KERNEL void amax_b16_kernel(const uint16_t* __restrict__ x, long long n,
 // load a pixel, a wave reads 256 contiguous bytes), times 1 / HW, into LDS.
 // Phase 2: wave w computes outputs w, w + 4, ...: lane l sums avg[c] W[c][n]
 // over c = l, l + 64, ... in order, a fixed xor tree joins the 64 lanes, lane
-// 0 adds the bias.  The same association on every run.
+// 0 adds the bias.  The same association on every run.  X3: x is a split
+// tensor, its lo plane xlo 4-byte words behind; a pixel adds hi + lo (exact).
 constexpr int HEAD_MAXC = 1024;
+template <bool X3>
 RINF_KERNEL void avgpool_fc_kernel(const uint32_t* __restrict__ x, const float* __restrict__ w,
                                    const float* __restrict__ bias, float* __restrict__ logits,
-                                   int HW, int C, int N, float inv) {
+                                   int HW, int C, int N, float inv, size_t xlo) {
   __shared__ float avg[HEAD_MAXC];
   const int row = blockIdx.x, tid = threadIdx.x, C2 = C / 2;
   const uint32_t* xr = x + (size_t)row * HW * C2;
@@ -177,8 +230,14 @@ RINF_KERNEL void avgpool_fc_kernel(const uint32_t* __restrict__ x, const float* 
     float s0 = 0.f, s1 = 0.f;
     for (int p = 0; p < HW; ++p) {
       const uint32_t u = xr[(size_t)p * C2 + c2];
-      s0 += bf_lo(u);
-      s1 += bf_hi(u);
+      if constexpr (X3) {
+        const uint32_t l = xr[xlo + (size_t)p * C2 + c2];
+        s0 += bf_lo(u) + bf_lo(l);
+        s1 += bf_hi(u) + bf_hi(l);
+      } else {
+        s0 += bf_lo(u);
+        s1 += bf_hi(u);
+      }
     }
     avg[2 * c2] = s0 * inv;
     avg[2 * c2 + 1] = s1 * inv;
@@ -226,6 +285,15 @@ void maxpool_infer_f8(const PoolShape& p, const void* xb, const float* inv_s, vo
                                                            inv_s, reinterpret_cast<uint4*>(y8));
 }
 
+void maxpool_infer_x3(const PoolShape& p, const void* x, void* y, hipStream_t st) {
+  if (p.C % 8 != 0 || p.pad >= p.k || (long long)p.N * p.H * p.W * p.C >= (1LL << 31) ||
+      (long long)p.N * p.OH * p.OW * p.C >= (1LL << 31))
+    throw std::runtime_error("maxpool_infer_x3: unsupported shape");
+  const long long n = (long long)p.N * p.OH * p.OW * (p.C / 8);
+  rinf::maxpool_infer_x3_kernel<<<grid1d(n), 256, 0, st>>>(p, reinterpret_cast<const uint4*>(x),
+                                                           reinterpret_cast<uint4*>(y));
+}
+
 void amax_b16(const void* xb, long long n, float* slot, hipStream_t st) {
   if (n < 1 || !xb || !slot) throw std::runtime_error("amax_b16: empty buffer");
   const long long b = (n / 8 + 255) / 256;
@@ -237,8 +305,17 @@ void avgpool_fc(const void* xb, const float* w, const float* bias, float* logits
                 int C, int N, hipStream_t st) {
   if (M < 1 || HW < 1 || N < 1 || C < 2 || C % 2 != 0 || C > rinf::HEAD_MAXC)
     throw std::runtime_error("avgpool_fc: unsupported shape");
-  rinf::avgpool_fc_kernel<<<M, 256, 0, st>>>(reinterpret_cast<const uint32_t*>(xb), w, bias, logits,
-                                             HW, C, N, 1.0f / (float)HW);
+  rinf::avgpool_fc_kernel<false><<<M, 256, 0, st>>>(reinterpret_cast<const uint32_t*>(xb), w, bias,
+                                                    logits, HW, C, N, 1.0f / (float)HW, 0);
+}
+
+void avgpool_fc_x3(const void* x, const float* w, const float* bias, float* logits, int M, int HW,
+                   int C, int N, hipStream_t st) {
+  if (M < 1 || HW < 1 || N < 1 || C < 2 || C % 2 != 0 || C > rinf::HEAD_MAXC)
+    throw std::runtime_error("avgpool_fc_x3: unsupported shape");
+  rinf::avgpool_fc_kernel<true><<<M, 256, 0, st>>>(reinterpret_cast<const uint32_t*>(x), w, bias,
+                                                   logits, HW, C, N, 1.0f / (float)HW,
+                                                   (size_t)M * HW * C / 2);
 }
 
 }  // namespace gops

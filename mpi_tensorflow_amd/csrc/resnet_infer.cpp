@@ -105,7 +105,10 @@ ResnetInferSizes ResnetInfer::ws_sizes(const ResnetInferPtrs& p, int m) {
   // the buffers serve every chunk of up to m rows (a ragged tail, a later
   // smaller call): the activations grow with the rows, the workspace does not,
   // so it is the maximum over every row count
-  for (int r = 1; r <= m; ++r) z.ws_floats = std::max(z.ws_floats, ws_floats_at(p, r));
+  if (p.x3)
+    z.act_bytes = 4;
+  else
+    for (int r = 1; r <= m; ++r) z.ws_floats = std::max(z.ws_floats, ws_floats_at(p, r));
   z.act[0] = std::max(blk, out_elems(n.stem));
   z.act[1] = std::max(blk, (long long)m * n.s2d.H * n.s2d.W * 16);
   z.act[2] = blk;
@@ -234,4 +237,47 @@ void ResnetInfer::eval_chunk_f8(const ResnetInferPtrs& p, uintptr_t x, int m, ui
   }
   gops::avgpool_fc(act[h], P<const float>(p.fc_w), P<const float>(p.fc_b), P<float>(logits), m,
                    n.fh * n.fw, 512, p.classes, s);
+}
+
+void ResnetInfer::eval_chunk_x3(const ResnetInferPtrs& p, uintptr_t x, int m, uintptr_t act0,
+                                uintptr_t act1, uintptr_t act2, uintptr_t logits, hipStream_t s) {
+  check(p, m);
+  if (!p.x3 || p.wx3.size() != 19 || p.fold_off.size() != 20 || !p.wt8x3 || !p.fold || !p.fc_w ||
+      !p.fc_b || std::find(p.wx3.begin(), p.wx3.end(), (uintptr_t)0) != p.wx3.end())
+    throw std::runtime_error("ResnetInfer: the bf16x3 forward needs x3 set (buffers of 4-byte "
+                             "elements), 19 split weight plane pairs, the split stem filter, 20 "
+                             "fold offsets, the fold table and the FC");
+  if (!x || !act0 || !act1 || !act2 || !logits) throw std::runtime_error("ResnetInfer: null buffer");
+  const Net n(p, m);
+  void* act[3] = {P<void>(act0), P<void>(act1), P<void>(act2)};
+  const float* fold = P<const float>(p.fold);
+  // conv i of the weight order runs BatchNorm 1 + i; bn 0 is the stem's
+  auto conv3 = [&](const ConvShape& cs, const void* xin, uintptr_t w, int bn, const void* res,
+                   bool relu, void* y) {
+    gops::X3Epi e;
+    const int off = p.fold_off[bn];
+    e.a = fold + off, e.b = fold + p.fold_total + off, e.res = res, e.relu = relu ? 1 : 0;
+    gops::x3conv(cs, xin, P<const void>(w), e, y, 0, s);
+  };
+  gops::s2d_stem_input_x3(P<const float>(x), m, p.H, p.W, n.stem.OH, n.stem.OW, act[1], s);
+  conv3(n.s2d, act[1], p.wt8x3, 0, nullptr, true, act[0]);
+  gops::maxpool_infer_x3(n.pool, act[0], act[1], s);
+  int h = 1, t = 0, u = 2;  // as run_bf16
+  size_t wi = 0;
+  for (const Block& b : n.blocks) {
+    const int bn = 1 + (int)wi;
+    if (b.down) {
+      conv3(b.ds, act[h], p.wx3[wi + 2], bn + 2, nullptr, false, act[u]);
+      conv3(b.c1, act[h], p.wx3[wi], bn, nullptr, true, act[t]);
+      conv3(b.c2, act[t], p.wx3[wi + 1], bn + 1, act[u], true, act[h]);
+      wi += 3;
+    } else {
+      conv3(b.c1, act[h], p.wx3[wi], bn, nullptr, true, act[t]);
+      conv3(b.c2, act[t], p.wx3[wi + 1], bn + 1, act[h], true, act[u]);
+      std::swap(h, u);
+      wi += 2;
+    }
+  }
+  gops::avgpool_fc_x3(act[h], P<const float>(p.fc_w), P<const float>(p.fc_b), P<float>(logits), m,
+                      n.fh * n.fw, 512, p.classes, s);
 }

@@ -12,7 +12,8 @@
 // Every BatchNorm is a folded per-channel (a, b) pair of bn_fold's table,
 // applied in the producing conv's epilogue (conv_fwd_affine_bf16); every
 // activation between two launches is bf16 (eval_chunk) or, behind the max pool
-// of eval_chunk_f8, e4m3 with one calibrated scale a tensor.  Each conv runs the plan
+// of eval_chunk_f8, e4m3 with one calibrated scale a tensor; eval_chunk_x3 runs
+// the same chain on bf16 hi / lo pairs (conv_x3.hip).  Each bf16 conv runs the plan
 // plan_fwd_bf16(shape, ConvHave{}) gives - what ops.conv_route reports.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -42,12 +43,22 @@ struct ResnetInferPtrs {
   std::vector<uintptr_t> w8;
   uintptr_t amax = 0, a2 = 0, scal = 0;
   bool calibrated = false;
+  // the bf16x3 forward (docs/ACCURACY.md "ResNet-18 bf16x3 inference"): the
+  // split stem filter (s2d_stem_weight_x3, planes [2][64][256]) and wsplit_x3's
+  // plane pairs [2][tap][k][c] in the order of wt.  x3: the buffers are sized
+  // for it - an activation element is a hi / lo pair, 4 bytes, and no conv
+  // takes a workspace
+  uintptr_t wt8x3 = 0;
+  std::vector<uintptr_t> wx3;
+  bool x3 = false;
 };
 
 struct ResnetInferSizes {
-  // three bf16 activation buffers (elements) and the fp32 split-K workspace (floats)
+  // three activation buffers (elements of act_bytes bytes: bf16, or a bf16x3
+  // pair) and the fp32 split-K workspace (floats)
   long long act[3] = {0, 0, 0};
   long long ws_floats = 0;
+  int act_bytes = 2;
 };
 
 class ResnetInfer {
@@ -73,5 +84,12 @@ class ResnetInfer {
   // suffice), no workspace: no conv splits K, so a row's logits do not depend
   // on the chunk it arrives in.  Refuses an uncalibrated or incomplete p.
   static void eval_chunk_f8(const ResnetInferPtrs& p, uintptr_t x, int m, uintptr_t act0,
+                            uintptr_t act1, uintptr_t act2, uintptr_t logits, hipStream_t s);
+  // the bf16x3 forward: s2d_stem_input_x3, the stem, maxpool_infer_x3, 19
+  // x3conv launches in eval_chunk's order, avgpool_fc_x3.  Every activation is
+  // a split tensor at the start of its buffer (ws_sizes with p.x3), no
+  // workspace: no conv splits K, so a row's logits do not depend on the chunk
+  // it arrives in.  Refuses an incomplete p.
+  static void eval_chunk_x3(const ResnetInferPtrs& p, uintptr_t x, int m, uintptr_t act0,
                             uintptr_t act1, uintptr_t act2, uintptr_t logits, hipStream_t s);
 };

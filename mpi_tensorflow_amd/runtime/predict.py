@@ -15,7 +15,10 @@ buffers, no graphs, no extra streams.  On the GPU a chunk of rows goes through
                    (docs/ACCURACY.md "ResNet-18 inference forward");
                    ResNet-18 (fp8): the same chain with the 19 convs behind
                    the max pool on calibrated e4m3 operands
-                   (docs/ACCURACY.md "ResNet-18 fp8 inference")
+                   (docs/ACCURACY.md "ResNet-18 fp8 inference");
+                   ResNet-18 (bf16x3): the whole chain on split tensors, every
+                   fp32 value a bf16 hi + lo pair, three bf16 MFMA products a
+                   multiply (docs/ACCURACY.md "ResNet-18 bf16x3 inference")
     predict_head  softmax, the mean over the views, scores and top-k
 
 once per view, one head launch per view and chunk.  On the CPU (and with
@@ -119,8 +122,8 @@ class Predictor:
         what it holds: the trained weights ("raw") or their moving average
         ("ema", --ema); the forward is the same.  `bn` (resnet18): every
         BatchNorm's (running mean, running variance) on the same device, used
-        in place.  resnet18 runs as dtype "bf16" or "fp8" on the native backend
-        or as "fp32" on the torch backend.  fp8: the activation scales come from
+        in place.  resnet18 runs as dtype "bf16", "fp8" or "bf16x3" on the native
+        backend or as "fp32" on the torch backend.  fp8: the activation scales come from
         `calibrate`; a predictor that has not been calibrated calibrates itself
         on the leading min(n, calib_rows) rows of its first input."""
         if weights not in C.PREDICT_WEIGHTS:
@@ -140,9 +143,10 @@ class Predictor:
             raise RuntimeError("the native Predictor needs a GPU")
         if model == "resnet18" and backend == "native" and dtype == "fp32":
             raise ValueError("resnet18: the native inference forward is bf16 (--dtype bf16); fp32 "
-                             "runs on the torch backend only")
-        if dtype == "fp8" and model != "resnet18":
-            raise ValueError(f"dtype fp8 supports resnet18 only, not {model}")
+                             "runs on the torch backend only, or --dtype bf16x3 for fp32-class "
+                             "results")
+        if dtype in ("fp8", "bf16x3") and model != "resnet18":
+            raise ValueError(f"dtype {dtype} supports resnet18 only, not {model}")
         if calib_rows < 1:
             raise ValueError("calib_rows must be positive")
         if dtype != "fp32" and (backend != "native" or model == "lenet5"):
@@ -157,6 +161,7 @@ class Predictor:
         self.classes = C.NUM_CLASSES
         self.bf16 = dtype == "bf16"
         self.fp8 = dtype == "fp8"
+        self.x3 = dtype == "bf16x3"
         self.calib_rows = int(calib_rows)
         self.calibrated_on = 0  # rows of the last calibration (fp8)
         self._ws: Optional[tuple] = None
@@ -296,7 +301,8 @@ class Predictor:
         (mode 0 only), the stem's space-to-depth filter, and bn_fold's job
         table and (a, b) table.  predict() re-derives them all.  fp8: wq_f8's
         codes and scales and f8_fold's tables as well; the bf16 copies are then
-        held only while `calibrate` runs."""
+        held only while `calibrate` runs.  bf16x3: wsplit_x3's plane pairs and
+        the split stem filter instead of the bf16 copies."""
         C_, dev = self._C, self.device
         pv = self.layout.views(self.params)
         convs, folds = [], ["bn1"]
@@ -309,7 +315,9 @@ class Predictor:
         p = C_.ResnetInferPtrs()
         p.H, p.W, p.classes = self.shape[0], self.shape[1], self.classes
         self.ptrs = p
-        if not self.fp8:
+        if self.x3:
+            self._make_x3_planes(pv, convs)
+        elif not self.fp8:
             self._hold_bf16_copies(True)
         rows, offs, o = [], [], 0
         for n in folds:
@@ -347,6 +355,24 @@ class Predictor:
         self._wblocks = blocks
         p.wt = wt
 
+    def _make_x3_planes(self, pv, convs) -> None:
+        """wsplit_x3's job table and the hi / lo plane pairs [2][tap][k][c] of the
+        19 convs in one buffer; the split stem filter [2][64][256]."""
+        p, dev = self.ptrs, self.device
+        self._wx3 = torch.empty(2 * sum(pv[n].numel() for n in convs), dtype=torch.bfloat16,
+                                device=dev)
+        self._wt8x3 = torch.empty(2 * 64 * 256, dtype=torch.bfloat16, device=dev)
+        rows, wx3, o, blocks = [], [], 0, 0
+        for n in convs:
+            R, S, Ci, K = pv[n].shape
+            out = self._wx3[o:o + 2 * pv[n].numel()]
+            o += 2 * pv[n].numel()
+            wx3.append(ptr(out))
+            rows.append([ptr(pv[n]), ptr(out), R * S, Ci, K, 0, blocks, 0])
+            blocks += K // 32
+        self._xjobs, self._xblocks = torch.tensor(rows, dtype=torch.int64).to(dev), blocks
+        p.wx3, p.wt8x3, p.x3 = wx3, ptr(self._wt8x3), True
+
     def _make_fp8_tables(self, pv, convs, offs, total) -> None:
         """wq_f8's job table, codes and scales; the calibration table (slot 0
         the pool output, 1 + i the output of conv i); f8_fold's job table (which
@@ -382,7 +408,12 @@ class Predictor:
         ops = self._C.ops
         if self._wcopy is not None:
             ops.wcvt_batch(ptr(self._wjobs), self._wjobs.shape[0], self._wblocks, s)
-        ops.s2d_stem_weight(ptr(self.layout.views(self.params)["conv1_w"]), 64, ptr(self._wt8), s)
+        w1 = ptr(self.layout.views(self.params)["conv1_w"])
+        if self.x3:
+            ops.wsplit_x3(ptr(self._xjobs), self._xjobs.shape[0], self._xblocks, s)
+            ops.s2d_stem_weight_x3(w1, 64, ptr(self._wt8x3), s)
+        else:
+            ops.s2d_stem_weight(w1, 64, ptr(self._wt8), s)
         ops.bn_fold(ptr(self._fjobs), self._fjobs.shape[0], self.ptrs.fold_total, BN_EPS,
                     ptr(self._fold), s)
         if self.fp8:
@@ -492,7 +523,10 @@ class Predictor:
     def _forward_native(self, x_ptr: int, m: int, ws, s: int) -> None:
         """logits of m fp32 rows at x_ptr into ws['logits'] (the labels are a
         zero buffer and no error counter is passed: nothing is counted here)."""
-        if self.fp8:
+        if self.x3:
+            self._C.ResnetInfer.eval_chunk_x3(self.ptrs, x_ptr, m, ptr(ws["act0"]), ptr(ws["act1"]),
+                                              ptr(ws["act2"]), ptr(ws["logits"]), s)
+        elif self.fp8:
             self._C.ResnetInfer.eval_chunk_f8(self.ptrs, x_ptr, m, ptr(ws["act0"]), ptr(ws["act1"]),
                                               ptr(ws["act2"]), ptr(ws["logits"]), s)
         elif self.model == "resnet18":

@@ -3,12 +3,16 @@ against GenericEngine.evaluate on the same weights, rows and device, in one
 process, the two alternating (docs/PERF_NOTES.md holds a run's figures).
 
     python scripts/resnet_predict_bench.py [--rows 1000] [--chunk 256] [--reps 25] [--windows 5]
-                                           [--dtype bf16|fp8]
+                                           [--dtype bf16|fp8|bf16x3] [--with-torch-fp32]
 
 --dtype fp8: the bf16 Predictor against an fp8 one on the same weights
 (calibrated on the leading 256 rows), and with it the fp8 A/Bs - the MFMA form
 (32x32x16 fp8_fp8 / 32x32x64 f8f6f4) and the loader of the 3x3 stride-1 convs
 (gather / halo) - all alternating in the one process.
+
+--dtype bf16x3: the bf16 Predictor against a bf16x3 one on the same weights;
+--with-torch-fp32 adds the torch-backend fp32 Predictor (the forward that serves
+fp32 checkpoints without bf16x3) to the same alternating windows.
 
 A window is `reps` passes over the `rows` device-resident fp32 rows between two
 synchronisations (a few hundred ms); the first window of each path is the
@@ -38,7 +42,8 @@ def main():
     ap.add_argument("--chunk", type=int, default=256)
     ap.add_argument("--reps", type=int, default=25)
     ap.add_argument("--windows", type=int, default=5)
-    ap.add_argument("--dtype", default="bf16", choices=("bf16", "fp8"))
+    ap.add_argument("--dtype", default="bf16", choices=("bf16", "fp8", "bf16x3"))
+    ap.add_argument("--with-torch-fp32", action="store_true")
     a = ap.parse_args()
     assert torch.cuda.is_available(), "needs a GPU"
     dev = torch.device("cuda:0")
@@ -80,6 +85,12 @@ def main():
 
         paths = {"predict": paths["predict"], "fp8_x16_gather": fp8(2, 1), "fp8_x64_gather": fp8(1, 1),
                  "fp8_x16_halo": fp8(2, 2), "fp8_x64_halo": fp8(1, 2)}
+    if a.dtype == "bf16x3":
+        prx = Predictor("resnet18", eng.params, dtype="bf16x3", bn=eng.bn)
+        paths = {"predict": paths["predict"], "bf16x3": lambda: prx.predict(xd, chunk=a.chunk)}
+        if a.with_torch_fp32:
+            prt = Predictor("resnet18", eng.params, dtype="fp32", backend="torch", bn=eng.bn)
+            paths["torch_fp32"] = lambda: prt.predict(xd, chunk=a.chunk)
     rate = {k: [] for k in paths}
     for _ in range(a.windows + 1):
         for k, fn in paths.items():
@@ -90,9 +101,12 @@ def main():
         rec[k + "_img_s"] = {"min": round(min(v)), "median": round(statistics.median(v)), "max": round(max(v))}
     base = "evaluate" if a.dtype == "bf16" else "predict"
     for k in rate:
-        if k != base and (a.dtype == "fp8" or k == "predict"):
+        if k != base and (a.dtype != "bf16" or k == "predict"):
             name = "ratio_of_medians" if a.dtype == "bf16" else k + "_over_bf16"
             rec[name] = round(rec[k + "_img_s"]["median"] / rec[base + "_img_s"]["median"], 3)
+    if "torch_fp32" in rate:
+        rec["bf16x3_over_torch_fp32"] = round(rec["bf16x3_img_s"]["median"]
+                                              / rec["torch_fp32_img_s"]["median"], 3)
     print(json.dumps(rec))
 
 
