@@ -1572,7 +1572,10 @@ void gather_soft(const int* labels2, const float* lam, const long long* step, in
 void gather_batch(const float* data, const int* labels, const long long* step, int n_local,
                   int batch, long long row_elems, float* xb, int* yb, hipStream_t st,
                   float lr_base, float lr_decay, float* lr_out) {
-  if (row_elems % 4 != 0 || batch > 256) throw std::runtime_error("gather_batch: unsupported shape");
+  // n_local <= batch: the offset's modulus is zero or negative and the rows lie
+  // behind the dataset (utils/data.py batch_offset raises the same way)
+  if (row_elems % 4 != 0 || batch > 256 || batch <= 0 || n_local <= batch)
+    throw std::runtime_error("gather_batch: unsupported shape");
   gather_batch_kernel<<<grid1d((long long)batch * row_elems / 4), 256, 0, st>>>(
       data, labels, step, n_local, batch, row_elems, xb, yb, lr_base, lr_decay, lr_out);
 }

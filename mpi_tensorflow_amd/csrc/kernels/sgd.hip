@@ -111,6 +111,8 @@ static inline int grid_for(long long n4) {
 void launch_sgd_momentum(float* w, const float* g, float* mom, long long n, long long l2_end,
                          float l2, float momentum, float gscale, const float* lr_ptr,
                          float lr_const, long long* step_ptr, hipStream_t s) {
+  if (n % 4) throw std::runtime_error("sgd_momentum: n % 4 != 0");
+  if (l2_end % 4) throw std::runtime_error("sgd_momentum: l2_end % 4 != 0");
   const long long n4 = n / 4;
   sgd_momentum_flat_kernel<<<grid_for(n4), 256, 0, s>>>(
       reinterpret_cast<float4*>(w), reinterpret_cast<const float4*>(g),
@@ -136,6 +138,7 @@ void launch_hash_words(const uint32_t* x, long long n, unsigned long long* out, 
 }
 
 void launch_scale(float* x, long long n, float a, hipStream_t s) {
+  if (n % 4) throw std::runtime_error("scale: n % 4 != 0");
   const long long n4 = n / 4;
   scale_kernel<<<grid_for(n4), 256, 0, s>>>(reinterpret_cast<float4*>(x), n4, a);
 }

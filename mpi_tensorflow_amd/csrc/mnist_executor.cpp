@@ -266,7 +266,8 @@ void MnistExecutor::sgd(hipStream_t s, float gscale) {
   sgd_range(s, 0, p_.total, gscale, true);
 }
 
-// momentum SGD over flat floats [lo, hi) (lo, hi multiples of 4); the L2
+// momentum SGD over flat floats [lo, hi) (lo, hi multiples of 4, as every
+// caller's are: the launcher throws on a ragged length or L2 boundary); the L2
 // prefix [0, l2_end) is clipped to the range; bump_step increments the
 // device step once (the last segment of a step)
 void MnistExecutor::sgd_range(hipStream_t s, long long lo, long long hi, float gscale,
