@@ -238,6 +238,60 @@ def parse_mix(spec: str):
     return kind, float(M)
 
 
+LARS_ETA = 0.001  # the trust coefficient of `--optimizer lars` without an ETA (You et al. 2017)
+
+
+@dataclasses.dataclass(frozen=True)
+class OptimizerSpec:
+    """A parsed --optimizer spec; eta / wd / nesterov are LARS's (docs/ACCURACY.md)."""
+    kind: str  # "momentum" | "lars"
+    eta: float = LARS_ETA
+    wd: float = 0.0
+    nesterov: bool = False
+
+
+def parse_optimizer(spec: str) -> OptimizerSpec:
+    """`momentum` (the reference's momentum SGD) or `lars[:ETA][,wd:V][,nesterov]`
+    (0 < ETA <= 1, default 0.001; V >= 0, default 0), the items after the first
+    in any order, each at most once; the definition: docs/ACCURACY.md."""
+    if not isinstance(spec, str) or not spec.strip():
+        raise ValueError("empty optimizer spec; expected e.g. 'momentum', 'lars', "
+                         "'lars:0.001,wd:5e-4,nesterov'")
+    seen = {}
+    for i, item in enumerate(spec.split(",")):
+        name, sep, val = item.strip().partition(":")
+        try:
+            if i == 0 and name == "momentum" and not sep:
+                v = True
+            elif i == 0 and name == "lars":
+                v = float(val) if sep else LARS_ETA
+            elif i > 0 and name == "wd" and sep:
+                v = float(val)
+            elif i > 0 and name == "nesterov" and not sep:
+                v = True
+            else:
+                raise ValueError
+            if v != v or abs(v) == float("inf"):
+                raise ValueError
+        except ValueError:
+            raise ValueError(f"bad item {item!r} in optimizer spec {spec!r}; expected momentum, or "
+                             f"lars[:ETA] then wd:V, nesterov") from None
+        if name in seen:
+            raise ValueError(f"optimizer spec {spec!r} names {name!r} twice")
+        seen[name] = v
+    if "momentum" in seen:
+        if len(seen) > 1:
+            raise ValueError(f"optimizer spec {spec!r}: momentum takes no items (wd and nesterov "
+                             f"are lars's; the momentum run's weight decay is --l2)")
+        return OptimizerSpec("momentum")
+    eta, wd = seen["lars"], seen.get("wd", 0.0)
+    if not 0.0 < eta <= 1.0:
+        raise ValueError(f"lars eta must be in (0, 1], got {eta:g}")
+    if wd < 0.0:
+        raise ValueError(f"lars wd must be at least 0, got {wd:g}")
+    return OptimizerSpec("lars", float(eta), float(wd), "nesterov" in seen)
+
+
 def check_label_smoothing(eps) -> float:
     """--label-smoothing EPS: a float with 0 <= EPS < 1."""
     try:
@@ -323,6 +377,11 @@ class TrainConfig:
     # target is the same blend of the two labels; None = rows stay apart
     mix: Optional[str] = None
     # learning rate / optimiser
+    # momentum (the reference's momentum SGD at one global rate, nothing extra
+    # runs) or lars[:ETA][,wd:V][,nesterov] (parse_optimizer): every weight tensor
+    # steps at its own trust ratio eta ||w|| / (||g|| + wd ||w||), taken on the
+    # device from the flat buffers (resnet18 and lenet5; docs/ACCURACY.md)
+    optimizer: str = "momentum"
     base_lr: float = BASE_LR
     lr_decay: float = LR_DECAY
     momentum: float = MOMENTUM
@@ -414,6 +473,10 @@ class TrainConfig:
         self.label_smoothing = check_label_smoothing(self.label_smoothing)
         if self.mix is not None:
             parse_mix(self.mix)
+        if parse_optimizer(self.optimizer).kind != "momentum" and self.model == "mnist_cnn":
+            raise ValueError("--optimizer lars does not support --model mnist_cnn: its SGD lives "
+                             "inside the backward launches, and moving it out is a separate piece "
+                             "of work; use lenet5 or resnet18")
         if self.predict_weights is not None and self.predict_weights not in PREDICT_WEIGHTS:
             raise ValueError(f"unknown predict weights {self.predict_weights!r}; choose from "
                              f"{PREDICT_WEIGHTS}")
@@ -460,6 +523,9 @@ class TrainConfig:
         if self.mix is not None or self.label_smoothing > 0.0:
             raise ValueError("--predict: mix and label smoothing are training-only (--mix, "
                              "--label-smoothing); a prediction has no target to soften")
+        if parse_optimizer(self.optimizer).kind != "momentum":
+            raise ValueError("--predict: --optimizer is training-only; a prediction updates "
+                             "no weights")
         if not self.resume:
             raise ValueError("--predict needs the checkpoint to predict with: --resume PATH")
         if (self.model == "resnet18" and self.dtype == "fp32" and self.backend != "torch"
@@ -573,6 +639,12 @@ def build_arg_parser(prog: str = "mpipy.py") -> argparse.ArgumentParser:
                         "partner row): every training row is blended with (mixup), or gets a box "
                         "of (cutmix), another row of its pass, redrawn each pass on the device; "
                         "the target blends the two labels alike (mixup:50 is the usual mixup)")
+    p.add_argument("--optimizer", default=d.optimizer, metavar="SPEC",
+                   help="momentum (the default: the reference's momentum SGD) or "
+                        "lars[:ETA][,wd:V][,nesterov]: layer-wise adaptive rate scaling for large "
+                        "global batches; every conv / FC weight tensor steps at its own trust "
+                        "ratio ETA |w| / (|g| + V |w|) (0 < ETA <= 1, default 0.001; V >= 0, "
+                        "default 0), biases and BatchNorm parameters at 1 (lenet5, resnet18)")
     p.add_argument("--base-lr", type=float, default=d.base_lr)
     p.add_argument("--lr-decay", type=float, default=d.lr_decay)
     p.add_argument("--momentum", type=float, default=d.momentum)

@@ -13,6 +13,7 @@
 #include "idx_loader.h"
 #include "kernels/augment.h"
 #include "kernels/ema.h"
+#include "kernels/lars.h"
 #include "kernels/mnist.h"
 #include "kernels/mnist_bf16.h"
 #include "kernels/ops_generic.h"
@@ -483,6 +484,17 @@ PYBIND11_MODULE(_C, m) {
                       step_const, S(s));
     check_launch();
   });
+  o.def("lars_step", [](uintptr_t w, uintptr_t g, uintptr_t mom, uintptr_t table, int ntensors,
+                        int nchunks, uintptr_t part, uintptr_t ratio, double eta, double wd,
+                        bool nesterov, float momentum, float gscale, uintptr_t lr_ptr,
+                        uintptr_t step_ptr, uintptr_t s) {
+    optim::launch_lars_step(P<float>(w), P<const float>(g), P<float>(mom),
+                            P<const long long>(table), ntensors, nchunks, P<float>(part),
+                            P<float>(ratio), eta, wd, nesterov, momentum, gscale,
+                            P<const float>(lr_ptr), P<long long>(step_ptr), S(s));
+    check_launch();
+  });
+  o.attr("LARS_CHUNK") = optim::kLarsChunk;
 
   // ------------------------------------------------------- generic ops
   auto g = m.def_submodule("ops", "generic NHWC layer kernels (conv/bn/pool/xent)");

@@ -119,6 +119,15 @@ class EngineBase:
             torch.cuda.synchronize(self.device)
 
 
+def momentum_sgd_only(cfg, who: str) -> None:
+    """The engines whose update is fused into their own launches run the
+    reference's momentum SGD and nothing else."""
+    opt = getattr(cfg, "optimizer", "momentum")
+    if C.parse_optimizer(opt).kind != "momentum":
+        raise ValueError(f"{who} updates by momentum SGD inside its own launches and cannot run "
+                         f"--optimizer {opt}; the op-by-op engine (GenericEngine) can")
+
+
 def graph_sizes(k: int, G: int) -> List[int]:
     """Lengths of the graphs k steps replay: the G-step graph, the remainder."""
     return ([G] if k >= G else []) + ([k % G] if k % G else [])

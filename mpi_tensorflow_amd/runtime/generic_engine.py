@@ -45,6 +45,7 @@ from ..utils.data import batch_offset
 from ..utils.devcache import DeviceArrayCache
 from .engine_common import (TUNE_REPLAYS, EngineBase, StateSnapshot, all_ranks_ok, graph_sizes,
                             pass_pieces, timed_replays)
+from .lars import LarsState, adapted, lars_update_
 from .shuffle import make_shuffler
 
 
@@ -86,6 +87,12 @@ class GenericEngine(EngineBase):
             raise ValueError(f"--ema: the op-by-op GPU engine keeps no average (model {cfg.model}); "
                              "mnist_cnn and lenet5 run their own engines on a GPU")
         self.init_ema()
+        # cfg.optimizer lars: the per-tensor trust ratios of the last step, in flat
+        # order (runtime/lars.py); None under the default momentum SGD
+        self.opt = C.parse_optimizer(cfg.optimizer)
+        self.lars = self.ratio = None
+        if self.opt.kind == "lars":
+            self.ratio = torch.ones(len(self.layout.specs)).to(device)
         self.wcache = None
         self.use_graph = cfg.graph and self.on_gpu
         self.graph_steps = max(1, cfg.graph_steps)
@@ -124,6 +131,9 @@ class GenericEngine(EngineBase):
             if self.wcache.njobs == 0:  # (LeNet-5 etc.: nothing to keep)
                 self.wcache = None
             self._wfresh = False  # the copies match the fp32 weights
+            if self.opt.kind == "lars":  # table, chunk sums and ratios: allocated before any capture
+                self.lars = LarsState.for_layout(self.layout, self.opt, device)
+                self.ratio = self.lars.ratio
         # cfg.shuffle / cfg.augment: the per-pass row order and shift / flip of train_x /
         # train_y (runtime/shuffle.py; keyed by the rank of the dropout stream, Q14): the
         # HIP gather on the native path, the host permutation and transform on the
@@ -302,6 +312,14 @@ class GenericEngine(EngineBase):
             C_.ops.lr_from_step(ptr(self.step_dev), self.n_local, self.B, self.cfg.base_lr,
                                 self.cfg.lr_decay, ptr(self.lr_dev), s)
         self._lr_fresh = False
+        if self.lars is not None:
+            # norms + update (csrc/kernels/lars.hip), then the conv weight copies of
+            # the updated weights in the launch that re-derives them anyway
+            self.lars.step(self.params.detach(), self.grads, self.mom, self.cfg.momentum, gscale,
+                           self.lr_dev, self.step_dev)
+            if self.wcache is not None:
+                self.wcache.refresh()
+            return
         if self.wcache is not None:  # + the bf16 layouts of the updated conv weights
             self.wcache.sgd(self.grads, self.mom, self.cfg.momentum, gscale, self.lr_dev,
                             self.step_dev)
@@ -331,6 +349,13 @@ class GenericEngine(EngineBase):
             if self.grad_sync:
                 all_reduce_grads_(self.comm, self.grads, self.cfg.grad_comm_dtype)
                 self.grads.mul_(1.0 / self.world)
+            if self.opt.kind == "lars":
+                pv, gv, mv = (self.layout.views(t)
+                              for t in (self.params.detach(), self.grads, self.mom))
+                for i, s in enumerate(self.layout.specs):
+                    self.ratio[i] = lars_update_(pv[s.name], gv[s.name], mv[s.name], adapted(s),
+                                                 self.opt, self.lr(), self.cfg.momentum)
+                return
             self.mom.mul_(self.cfg.momentum).add_(self.grads)
             self.params.sub_(self.lr() * self.mom)
 
@@ -557,8 +582,14 @@ def make_image_engine(cfg: C.TrainConfig, train_x: np.ndarray, train_y: np.ndarr
     its 3- and 6-channel convs and its FCs are VALU work whatever the operand
     type (the op-by-op engine's "bf16" LeNet ran the same fp32 math 6x
     slower), so --dtype bf16 runs the fp32 executor, says so, and the
-    engine's `dtype` reports fp32."""
-    if cfg.model == "lenet5" and device.type == "cuda":
+    engine's `dtype` reports fp32.  The fused executor's update is momentum
+    SGD inside its second launch: any other --optimizer trains LeNet-5 on the
+    op-by-op engine, and says so."""
+    if cfg.model == "lenet5" and device.type == "cuda" and cfg.optimizer != "momentum":
+        if rank == 0:
+            print(f"[lenet5] --optimizer {cfg.optimizer}: the fused executor updates by momentum "
+                  "SGD only; running the op-by-op engine", flush=True)
+    elif cfg.model == "lenet5" and device.type == "cuda":
         from .lenet_engine import NativeLenetEngine
 
         if cfg.dtype != "fp32":

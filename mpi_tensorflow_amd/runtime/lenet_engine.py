@@ -25,7 +25,8 @@ from ..ops import native, ptr, stream_handle
 from ..parallel.comm import DeviceComm, XgmiDeviceComm
 from ..utils.devcache import DeviceArrayCache
 from .engine_common import (TUNE_REPLAYS, EngineBase, GraphStepDriver, StateSnapshot,
-                            all_ranks_ok, timed_replays, xgmi_healthy, xgmi_step_matches)
+                            all_ranks_ok, momentum_sgd_only, timed_replays, xgmi_healthy,
+                            xgmi_step_matches)
 from .shuffle import make_shuffler
 
 # the executor's xGMI sync modes (csrc/lenet_executor.h XGMI_*)
@@ -53,6 +54,7 @@ class NativeLenetEngine(GraphStepDriver, EngineBase):
         if cfg.dtype != "fp32":
             raise NotImplementedError("the fused LeNet-5 kernels are fp32 (VALU convs over 3 / 6 "
                                       "channels); use the generic engine for bf16")
+        momentum_sgd_only(cfg, "NativeLenetEngine")
         super().__init__(cfg, train_x.shape[0], device, rank, world, comm, force_sync)
         self.model = make_model("lenet5")
         self.layout = self.model.layout

@@ -39,7 +39,7 @@ from ..utils import rng
 from ..utils.data import batch_offset
 from .engine_common import XGMI_STEP_RTOL  # noqa: F401  (re-exported: the tests' bound)
 from .engine_common import (TUNE_REPLAYS, EngineBase, GraphStepDriver, StateSnapshot, all_ranks_ok,
-                            timed_replays, xgmi_healthy, xgmi_step_matches)
+                            momentum_sgd_only, timed_replays, xgmi_healthy, xgmi_step_matches)
 from .shuffle import make_shuffler
 
 # sync_schedule="auto": the single-communicator gradient-sync schedules
@@ -174,6 +174,7 @@ class NativeMnistEngine(GraphStepDriver, MnistEngineBase):
         LDS.  Equal in isolation (8.0 vs 8.3 us), but 3 us SLOWER in the step
         (10.0 vs 6.9 us: the 4-byte scattered a2t stores of 256 blocks leave
         partial lines in every XCD's L2), so off (docs/PERF_NOTES.md)."""
+        momentum_sgd_only(cfg, "NativeMnistEngine")
         super().__init__(cfg, train_x, train_y, device, rank, world, comm, force_sync)
         if device.type != "cuda":
             raise RuntimeError("NativeMnistEngine needs a GPU")

@@ -79,10 +79,12 @@ class RunSummary:
     # --label-smoothing / --mix only: the run's soft-target flags as given
     label_smoothing: Optional[float] = None
     mix: Optional[str] = None
+    # --optimizer other than momentum only: the spec as given
+    optimizer: Optional[str] = None
 
     _OPTIONAL = ("final_test_loss", "final_val_error", "final_val_loss",
                  "final_ema_test_error_local", "final_ema_test_error_global",
-                 "label_smoothing", "mix")
+                 "label_smoothing", "mix", "optimizer")
 
     def as_dict(self) -> Dict:
         d = dataclasses.asdict(self)
@@ -541,7 +543,8 @@ class Trainer:
             final_test_loss=extra.get("test_loss"), final_val_error=extra.get("val_error"),
             final_val_loss=extra.get("val_loss"),
             final_ema_test_error_local=ema_err, final_ema_test_error_global=ema_err_g,
-            label_smoothing=cfg.label_smoothing if cfg.label_smoothing > 0 else None, mix=cfg.mix)
+            label_smoothing=cfg.label_smoothing if cfg.label_smoothing > 0 else None, mix=cfg.mix,
+            optimizer=cfg.optimizer if cfg.optimizer != "momentum" else None)
         self.metrics.write(final=True, **summary.as_dict(), **extra)
         if cfg.ckpt:
             self.save_checkpoint(cfg.ckpt)
