@@ -81,8 +81,10 @@ XGMI_MODES = ("two-phase", "push", "pull")
 # fp8 (OCP e4m3, post-training): --predict --model resnet18 on the native GPU path only
 # bf16x3 (every fp32 value as a bf16 hi + lo pair, three bf16 MFMA products a
 # multiply: fp32-class results): the same path and restrictions as fp8
-DTYPES = ("fp32", "bf16", "fp8", "bf16x3")
-PREDICT_CALIB_ROWS = 256  # rows an fp8 predictor calibrates itself on by default
+# mxfp4 (OCP MXFP4 weights - e2m1 codes, one E8M0 scale per 32 input channels -
+# under fp8's calibrated e4m3 activations): the same path and restrictions as fp8
+DTYPES = ("fp32", "bf16", "fp8", "bf16x3", "mxfp4")
+PREDICT_CALIB_ROWS = 256  # rows an fp8 / mxfp4 predictor calibrates itself on by default
 # --augment: what is shifted in from outside the image unless the spec says
 # fill:V.  MNIST: the normalised raw 0 pixel, (0 - 127.5) / 255; the others:
 # zero-padding of a centred image
@@ -419,7 +421,7 @@ class TrainConfig:
     # raw | ema: the checkpoint's trained weights or their moving average (--ema);
     # None = raw, not named (the JSON record then has no "weights" entry)
     predict_weights: Optional[str] = None
-    # --dtype fp8: leading rows of the source the activation scales are calibrated
+    # --dtype fp8 / mxfp4: leading rows of the source the activation scales are calibrated
     # on (None = PREDICT_CALIB_ROWS, not named)
     predict_calib: Optional[int] = None
     quiet: bool = False
@@ -487,14 +489,15 @@ class TrainConfig:
             if self.effective_eval_every() == 0:
                 raise ValueError("--ckpt-best needs periodic evaluation (--eval-every > 0)")
             self.eval_metrics = True
-        if self.dtype == "fp8":
+        if self.dtype in ("fp8", "mxfp4"):
+            d = self.dtype
             if self.predict is None:
-                raise ValueError("--dtype fp8 is inference only: it needs --predict SRC (training "
+                raise ValueError(f"--dtype {d} is inference only: it needs --predict SRC (training "
                                  "runs in fp32 or bf16)")
             if self.model != "resnet18":
-                raise ValueError(f"--dtype fp8 supports --model resnet18 only, not {self.model}")
+                raise ValueError(f"--dtype {d} supports --model resnet18 only, not {self.model}")
             if self.backend == "torch" or self.device == "cpu":
-                raise ValueError("--dtype fp8 runs on the native GPU forward only: not with "
+                raise ValueError(f"--dtype {d} runs on the native GPU forward only: not with "
                                  "--backend torch or --device cpu")
         if self.dtype == "bf16x3":
             if self.predict is None:
@@ -506,7 +509,7 @@ class TrainConfig:
                 raise ValueError("--dtype bf16x3 runs on the native GPU forward only: not with "
                                  "--backend torch or --device cpu")
         if self.predict_calib is not None:
-            if self.dtype != "fp8":
+            if self.dtype not in ("fp8", "mxfp4"):  # (mxfp4 calibrates the same activations)
                 raise ValueError("--predict-calib needs --dtype fp8")
             if self.predict_calib < 1:
                 raise ValueError(f"--predict-calib must be positive, got {self.predict_calib}")
@@ -585,7 +588,10 @@ def build_arg_parser(prog: str = "mpipy.py") -> argparse.ArgumentParser:
                    help="rows per step and rank (mpipy.py:20), any positive size; the native "
                         "MNIST engine computes ceil(B / 32) * 32 rows a step, the rows past B "
                         "adding nothing to the gradients")
-    p.add_argument("--dtype", default=d.dtype, choices=DTYPES)
+    p.add_argument("--dtype", default=d.dtype, choices=DTYPES,
+                   help="fp32 / bf16 train and predict; fp8 (e4m3 convs), mxfp4 (MXFP4 weights "
+                        "under e4m3 activations) and bf16x3 (fp32-class) are --predict --model "
+                        "resnet18 only")
     p.add_argument("--sync", default=d.sync, choices=SYNC_MODES)
     p.add_argument("--sync-every", type=int, default=d.sync_every)
     p.add_argument("--sync-schedule", default=d.sync_schedule, choices=SYNC_SCHEDULES,
@@ -688,7 +694,7 @@ def build_arg_parser(prog: str = "mpipy.py") -> argparse.ArgumentParser:
                         "their moving average (ema: a checkpoint of an --ema run); when given, "
                         "the JSON record names it under \"weights\"")
     p.add_argument("--predict-calib", type=int, default=d.predict_calib, metavar="ROWS",
-                   help="--dtype fp8: calibrate the activation scales on the leading ROWS rows "
+                   help="--dtype fp8 / mxfp4: calibrate the activation scales on the leading ROWS rows "
                         f"of SRC (default {PREDICT_CALIB_ROWS})")
     p.add_argument("--quiet", action="store_true")
     p.add_argument("--collective-timeout-s", type=float, default=d.collective_timeout_s,

@@ -745,6 +745,29 @@ PYBIND11_MODULE(_C, m) {
     gops::maxpool_infer_f8(p, P<const void>(xb), P<const float>(inv_s), P<void>(y8), S(st));
     check_launch();
   });
+  // the MXFP4-weight inference ops (conv_mx4.hip)
+  g.def("mx4conv", [](const gops::ConvShape& s, uintptr_t x8, uintptr_t w4, uintptr_t a2,
+                      uintptr_t b, uintptr_t res, uintptr_t s_res, uintptr_t inv_s_out, bool relu,
+                      uintptr_t y, bool out_bf16, uintptr_t st, int form) {
+    const gops::F8Epi e{P<const float>(a2), P<const float>(b), P<const void>(res),
+                        P<const float>(s_res), P<const float>(inv_s_out), relu ? 1 : 0};
+    gops::mx4conv(s, P<const void>(x8), P<const void>(w4), e, P<void>(y), out_bf16, form, S(st));
+    check_launch();
+  }, py::arg("s"), py::arg("x8"), py::arg("w4"), py::arg("a2"), py::arg("b"), py::arg("res"),
+     py::arg("s_res"), py::arg("inv_s_out"), py::arg("relu"), py::arg("y"), py::arg("out_bf16"),
+     py::arg("st"), py::arg("form") = 0);
+  // read-only: the tile and loader mx4conv runs for a shape ("form": 1 gather, 2 halo)
+  g.def("mx4conv_plan", [](const gops::ConvShape& s, int form) {
+    const gops::F8Plan p = gops::mx4conv_plan(s, form);
+    py::dict d;
+    d["bm"] = p.bm;
+    d["form"] = p.form;
+    return d;
+  }, py::arg("s"), py::arg("form") = 0);
+  g.def("wq_mx4", [](uintptr_t jobs, int njobs, long long nblocks, uintptr_t st) {
+    gops::wq_mx4(P<const long long>(jobs), njobs, nblocks, S(st));
+    check_launch();
+  });
   // the bf16x3 (split-operand bf16) inference ops (conv_x3.hip, resnet_infer.hip)
   g.def("x3conv", [](const gops::ConvShape& s, uintptr_t x, uintptr_t w, uintptr_t a, uintptr_t b,
                      uintptr_t res, bool relu, uintptr_t y, uintptr_t st, int form) {
@@ -1265,6 +1288,7 @@ PYBIND11_MODULE(_C, m) {
       .def_readwrite("a2", &ResnetInferPtrs::a2)
       .def_readwrite("scal", &ResnetInferPtrs::scal)
       .def_readwrite("calibrated", &ResnetInferPtrs::calibrated)
+      .def_readwrite("mx4", &ResnetInferPtrs::mx4)
       .def_readwrite("wt8x3", &ResnetInferPtrs::wt8x3)
       .def_readwrite("wx3", &ResnetInferPtrs::wx3)
       .def_readwrite("x3", &ResnetInferPtrs::x3);

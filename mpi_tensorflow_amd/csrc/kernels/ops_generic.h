@@ -260,6 +260,26 @@ void f8_fold(const long long* jobs, int njobs, const float* fold, const float* s
 void maxpool_infer_f8(const PoolShape& p, const void* xb, const float* inv_s, void* y8,
                       hipStream_t st);
 void amax_b16(const void* xb, long long n, float* slot, hipStream_t st);
+// conv_mx4.hip: the MXFP4-weight inference convs (docs/ACCURACY.md "ResNet-18
+// mxfp4 inference"): e4m3 activations, e2m1 weights with one E8M0 scale per 32
+// input channels of a (tap, output channel), applied inside the MFMA.  Weights
+// are slabs, one per (64-wide output-channel tile nt, 64-channel chunk ch), slab
+// nt * (C / 64) + ch, taps * 2176 bytes each: per tap, per 32-column group g, per
+// half h of the chunk, per column r, the 16 bytes of channels 64 ch + 32 h +
+// [0, 32) of output channel 64 nt + 32 g + r (the even channel in the low
+// nibble); behind the taps * 2048 code bytes one scale byte (E + 127) a block in
+// the same (tap, g, h, r) order.
+// f8conv's shapes, tile rule, forms (0 the planner's choice: halo where it
+// applies) and epilogue, with a2[k] = a[k] s_in; no split-K, no atomics
+F8Plan mx4conv_plan(const ConvShape& s, int form);
+void mx4conv(const ConvShape& s, const void* x, const void* w, const F8Epi& e, void* y,
+             bool out_bf16, int form, hipStream_t st);
+// every conv's weights quantised into slabs in one launch: jobs = device int64
+// [njobs][8] = {w (HWIO fp32), out (slabs), taps, C, K, 0, first block, 0},
+// (K / 64) (C / 64) blocks a job, first blocks ascending.  Per block of 32
+// channels: E the least integer with 6 2^E >= max |w| (0 for zeros, held to
+// [-100, 100]), the codes e2m1_rne(w / 2^E), a tie to the even magnitude index
+void wq_mx4(const long long* jobs, int njobs, long long nblocks, hipStream_t st);
 // conv_x3.hip: the split-operand bf16 ("bf16x3") inference convs (docs/ACCURACY.md
 // "ResNet-18 bf16x3 inference").  A split tensor is two bf16 planes of the
 // tensor's shape, hi = bf16_rne(v) then lo = bf16_rne(v - hi), numel elements

@@ -217,7 +217,10 @@ void ResnetInfer::eval_chunk_f8(const ResnetInferPtrs& p, uintptr_t x, int m, ui
     const int off = p.fold_off[1 + i];
     e.a2 = a2 + off, e.b = fold + p.fold_total + off;
     e.res = res, e.s_res = scal + i, e.inv_s_out = scal + 19 + i, e.relu = relu ? 1 : 0;
-    gops::f8conv(cs, xin, P<const void>(p.w8[i]), e, y, last, 0, 0, s);
+    if (p.mx4)
+      gops::mx4conv(cs, xin, P<const void>(p.w8[i]), e, y, last, 0, s);
+    else
+      gops::f8conv(cs, xin, P<const void>(p.w8[i]), e, y, last, 0, 0, s);
   };
   int h = 1, t = 0, u = 2;
   size_t wi = 0;

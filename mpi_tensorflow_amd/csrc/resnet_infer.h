@@ -43,6 +43,10 @@ struct ResnetInferPtrs {
   std::vector<uintptr_t> w8;
   uintptr_t amax = 0, a2 = 0, scal = 0;
   bool calibrated = false;
+  // the mxfp4 forward (docs/ACCURACY.md "ResNet-18 mxfp4 inference") is the fp8
+  // forward with MXFP4 weights: w8 holds wq_mx4's slabs, the convs are mx4conv,
+  // and f8_fold ran on a weight-scale table of ones
+  bool mx4 = false;
   // the bf16x3 forward (docs/ACCURACY.md "ResNet-18 bf16x3 inference"): the
   // split stem filter (s2d_stem_weight_x3, planes [2][64][256]) and wsplit_x3's
   // plane pairs [2][tap][k][c] in the order of wt.  x3: the buffers are sized
@@ -83,6 +87,7 @@ class ResnetInfer {
   // last one writes bf16), avgpool_fc.  The same three buffers (their bytes
   // suffice), no workspace: no conv splits K, so a row's logits do not depend
   // on the chunk it arrives in.  Refuses an uncalibrated or incomplete p.
+  // p.mx4: the same chain with 19 mx4conv launches on wq_mx4's slabs.
   static void eval_chunk_f8(const ResnetInferPtrs& p, uintptr_t x, int m, uintptr_t act0,
                             uintptr_t act1, uintptr_t act2, uintptr_t logits, hipStream_t s);
   // the bf16x3 forward: s2d_stem_input_x3, the stem, maxpool_infer_x3, 19

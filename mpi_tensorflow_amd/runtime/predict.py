@@ -16,6 +16,9 @@ buffers, no graphs, no extra streams.  On the GPU a chunk of rows goes through
                    ResNet-18 (fp8): the same chain with the 19 convs behind
                    the max pool on calibrated e4m3 operands
                    (docs/ACCURACY.md "ResNet-18 fp8 inference");
+                   ResNet-18 (mxfp4): the fp8 chain with MXFP4 weights, e2m1
+                   codes and one E8M0 scale per 32 input channels
+                   (docs/ACCURACY.md "ResNet-18 mxfp4 inference");
                    ResNet-18 (bf16x3): the whole chain on split tensors, every
                    fp32 value a bf16 hi + lo pair, three bf16 MFMA products a
                    multiply (docs/ACCURACY.md "ResNet-18 bf16x3 inference")
@@ -122,8 +125,8 @@ class Predictor:
         what it holds: the trained weights ("raw") or their moving average
         ("ema", --ema); the forward is the same.  `bn` (resnet18): every
         BatchNorm's (running mean, running variance) on the same device, used
-        in place.  resnet18 runs as dtype "bf16", "fp8" or "bf16x3" on the native
-        backend or as "fp32" on the torch backend.  fp8: the activation scales come from
+        in place.  resnet18 runs as dtype "bf16", "fp8", "mxfp4" or "bf16x3" on the native
+        backend or as "fp32" on the torch backend.  fp8, mxfp4: the activation scales come from
         `calibrate`; a predictor that has not been calibrated calibrates itself
         on the leading min(n, calib_rows) rows of its first input."""
         if weights not in C.PREDICT_WEIGHTS:
@@ -145,7 +148,7 @@ class Predictor:
             raise ValueError("resnet18: the native inference forward is bf16 (--dtype bf16); fp32 "
                              "runs on the torch backend only, or --dtype bf16x3 for fp32-class "
                              "results")
-        if dtype in ("fp8", "bf16x3") and model != "resnet18":
+        if dtype in ("fp8", "mxfp4", "bf16x3") and model != "resnet18":
             raise ValueError(f"dtype {dtype} supports resnet18 only, not {model}")
         if calib_rows < 1:
             raise ValueError("calib_rows must be positive")
@@ -160,7 +163,8 @@ class Predictor:
         self.shape = input_shape(model)
         self.classes = C.NUM_CLASSES
         self.bf16 = dtype == "bf16"
-        self.fp8 = dtype == "fp8"
+        self.mx4 = dtype == "mxfp4"  # the fp8 chain (e4m3 activations) on MXFP4 weights
+        self.fp8 = dtype == "fp8" or self.mx4
         self.x3 = dtype == "bf16x3"
         self.calib_rows = int(calib_rows)
         self.calibrated_on = 0  # rows of the last calibration (fp8)
@@ -376,20 +380,25 @@ class Predictor:
     def _make_fp8_tables(self, pv, convs, offs, total) -> None:
         """wq_f8's job table, codes and scales; the calibration table (slot 0
         the pool output, 1 + i the output of conv i); f8_fold's job table (which
-        tensor each conv reads, writes and adds) and its outputs."""
+        tensor each conv reads, writes and adds) and its outputs.  mxfp4:
+        wq_mx4's job table and slabs (a block per slab, taps * 2176 bytes:
+        half a byte a weight and a scale byte per 32) and a weight-scale
+        table of ones, which no launch writes."""
         p, dev = self.ptrs, self.device
         f32 = dict(dtype=torch.float32, device=dev)
-        self._w8 = torch.empty(sum(pv[n].numel() for n in convs), dtype=torch.uint8, device=dev)
-        self._sw, self._a2 = torch.empty(total, **f32), torch.empty(total, **f32)
+        sizes = [pv[n].numel() * 17 // 32 if self.mx4 else pv[n].numel() for n in convs]
+        self._w8 = torch.empty(sum(sizes), dtype=torch.uint8, device=dev)
+        self._sw = torch.ones(total, **f32) if self.mx4 else torch.empty(total, **f32)
+        self._a2 = torch.empty(total, **f32)
         self._amax, self._scal = torch.zeros(len(convs) + 1, **f32), torch.empty(2 * len(convs) + 1, **f32)
         rows, w8, o, blocks = [], [], 0, 0
         for i, n in enumerate(convs):
             R, S, Ci, K = pv[n].shape
-            out = self._w8[o:o + pv[n].numel()]
-            o += pv[n].numel()
+            out = self._w8[o:o + sizes[i]]
+            o += sizes[i]
             w8.append(ptr(out))
             rows.append([ptr(pv[n]), ptr(out), R * S, Ci, K, offs[1 + i], blocks, 0])
-            blocks += K // 32
+            blocks += (K // 64) * (Ci // 64) if self.mx4 else K // 32
         self._qjobs, self._qblocks = torch.tensor(rows, dtype=torch.int64).to(dev), blocks
         rows, i, src = [], 0, 0  # src: the slot of the block input
         for name, cin, c, s, down in self._generic._blocks():
@@ -401,6 +410,7 @@ class Predictor:
             src, i = 2 + i, i + (3 if down else 2)
         self._f8jobs = torch.tensor(rows, dtype=torch.int64).to(dev)
         p.w8, p.amax, p.a2, p.scal = w8, ptr(self._amax), ptr(self._a2), ptr(self._scal)
+        p.mx4 = self.mx4
 
     def _derive_resnet(self, s: int) -> None:
         """The bf16 weight operands and the folded BatchNorms, from the
@@ -417,7 +427,10 @@ class Predictor:
         ops.bn_fold(ptr(self._fjobs), self._fjobs.shape[0], self.ptrs.fold_total, BN_EPS,
                     ptr(self._fold), s)
         if self.fp8:
-            ops.wq_f8(ptr(self._qjobs), self._qjobs.shape[0], self._qblocks, ptr(self._sw), s)
+            if self.mx4:
+                ops.wq_mx4(ptr(self._qjobs), self._qjobs.shape[0], self._qblocks, s)
+            else:
+                ops.wq_f8(ptr(self._qjobs), self._qjobs.shape[0], self._qblocks, ptr(self._sw), s)
             if self.ptrs.calibrated:
                 self._f8_fold(s)
 
@@ -427,12 +440,13 @@ class Predictor:
 
     @torch.no_grad()
     def calibrate(self, x, chunk: int = RESNET_CHUNK) -> int:
-        """fp8: the activation scales from the rows x.  Zeroes the amax table,
+        """fp8, mxfp4: the activation scales from the rows x.  Zeroes the amax table,
         runs the bf16 forward over x with a max |value| launch behind every
         tensor the fp8 forward quantises (calibrate_chunk), and folds.  The
         scales stay until the next call.  -> the rows used."""
         if not self.fp8:
-            raise ValueError("calibrate: only a dtype fp8 predictor has scales to calibrate")
+            raise ValueError("calibrate: only a dtype fp8 or mxfp4 predictor has scales to "
+                             "calibrate")
         xd = self._rows(x)
         n = int(xd.shape[0])
         if n < 1 or chunk < 1:

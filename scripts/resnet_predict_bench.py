@@ -3,12 +3,16 @@ against GenericEngine.evaluate on the same weights, rows and device, in one
 process, the two alternating (docs/PERF_NOTES.md holds a run's figures).
 
     python scripts/resnet_predict_bench.py [--rows 1000] [--chunk 256] [--reps 25] [--windows 5]
-                                           [--dtype bf16|fp8|bf16x3] [--with-torch-fp32]
+                                           [--dtype bf16|fp8|bf16x3|mxfp4] [--with-torch-fp32]
 
 --dtype fp8: the bf16 Predictor against an fp8 one on the same weights
 (calibrated on the leading 256 rows), and with it the fp8 A/Bs - the MFMA form
 (32x32x16 fp8_fp8 / 32x32x64 f8f6f4) and the loader of the 3x3 stride-1 convs
 (gather / halo) - all alternating in the one process.
+
+--dtype mxfp4: the bf16, fp8 and mxfp4 Predictors on the same weights, the two
+quantised ones calibrated on the same leading 256 rows, alternating; the record
+adds mxfp4 over fp8 and the bytes of the two weight buffers.
 
 --dtype bf16x3: the bf16 Predictor against a bf16x3 one on the same weights;
 --with-torch-fp32 adds the torch-backend fp32 Predictor (the forward that serves
@@ -42,7 +46,7 @@ def main():
     ap.add_argument("--chunk", type=int, default=256)
     ap.add_argument("--reps", type=int, default=25)
     ap.add_argument("--windows", type=int, default=5)
-    ap.add_argument("--dtype", default="bf16", choices=("bf16", "fp8", "bf16x3"))
+    ap.add_argument("--dtype", default="bf16", choices=("bf16", "fp8", "bf16x3", "mxfp4"))
     ap.add_argument("--with-torch-fp32", action="store_true")
     a = ap.parse_args()
     assert torch.cuda.is_available(), "needs a GPU"
@@ -85,6 +89,13 @@ def main():
 
         paths = {"predict": paths["predict"], "fp8_x16_gather": fp8(2, 1), "fp8_x64_gather": fp8(1, 1),
                  "fp8_x16_halo": fp8(2, 2), "fp8_x64_halo": fp8(1, 2)}
+    if a.dtype == "mxfp4":
+        pr8 = Predictor("resnet18", eng.params, dtype="fp8", bn=eng.bn)
+        pr4 = Predictor("resnet18", eng.params, dtype="mxfp4", bn=eng.bn)
+        pr8.calibrate(xd[:256], chunk=a.chunk)
+        pr4.calibrate(xd[:256], chunk=a.chunk)
+        paths = {"predict": paths["predict"], "fp8": lambda: pr8.predict(xd, chunk=a.chunk),
+                 "mxfp4": lambda: pr4.predict(xd, chunk=a.chunk)}
     if a.dtype == "bf16x3":
         prx = Predictor("resnet18", eng.params, dtype="bf16x3", bn=eng.bn)
         paths = {"predict": paths["predict"], "bf16x3": lambda: prx.predict(xd, chunk=a.chunk)}
@@ -104,6 +115,9 @@ def main():
         if k != base and (a.dtype != "bf16" or k == "predict"):
             name = "ratio_of_medians" if a.dtype == "bf16" else k + "_over_bf16"
             rec[name] = round(rec[k + "_img_s"]["median"] / rec[base + "_img_s"]["median"], 3)
+    if "mxfp4" in rate:  # the weight operands' bytes, read from the allocated buffers
+        rec["mxfp4_over_fp8"] = round(rec["mxfp4_img_s"]["median"] / rec["fp8_img_s"]["median"], 3)
+        rec["weight_bytes"] = {"fp8": pr8._w8.numel(), "mxfp4": pr4._w8.numel()}
     if "torch_fp32" in rate:
         rec["bf16x3_over_torch_fp32"] = round(rec["bf16x3_img_s"]["median"]
                                               / rec["torch_fp32_img_s"]["median"], 3)
