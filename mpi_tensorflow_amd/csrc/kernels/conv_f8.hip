@@ -6,8 +6,9 @@
 // operands are one byte an element, so a K tile of one tap x 64 channels is 64
 // bytes a row of A (activations, fp8 NHWC) and of B (weights, fp8
 // [tap][k][c], c contiguous, written by wq_f8):
-//   * 256 threads, 2 x 2 waves; block tiles 128 x 64 and 64 x 64 (f8conv_plan,
-//     by M), one 32 x 32 accumulator per 32 rows of a wave;
+//   * lowp_conv_core.h's geometry (256 threads, 2 x 2 waves, block tiles 128 x
+//     64 and 64 x 64 by byte_conv_plan's rule, no split-K, no atomics), its A
+//     loaders and its epilogue (F8Epi);
 //   * lane (r, h) of a wave reads bytes [32 h, 32 h + 32) of LDS row r of A and
 //     of B (two ds_read_b128 each) - the SAME slot-to-k mapping for both
 //     operands, and the two lane groups cover the 64-byte K tile once, so the
@@ -23,166 +24,70 @@
 //     slots a 16-lane group) collide 2-way on 3 of 16 lanes; reads outnumber
 //     writes;
 //   * 16-byte global loads, double-buffered LDS, the next tile's loads in
-//     flight during this tile's MFMAs, one barrier a K tile, fwd_kernel's
-//     XCD-aware block order;
-//   * NO split-K and no atomics: one wave accumulates an output element over
-//     the K tiles in one fixed order, so a row's result does not depend on the
-//     rows that share its launch (a small chunk fills few CUs on layer 4; that
-//     is accepted).
+//     flight during this tile's MFMAs, one barrier a K tile (a small chunk
+//     fills few CUs on layer 4; that is accepted).
 // Two loaders (template flag HALO):
 //   gather  R in {1, 3}, stride in {1, 2}: each K tile gathers its BM input
-//           pixels of one tap (zeros outside the image); K tiles tap-major;
-//   halo    3x3 / stride 1 / pad 1: per 64-channel chunk the contiguous run of
-//           input pixels from one image row above the block's output pixels to
-//           one below (BM + 2 W + 2 rows of 64 bytes) is staged once, double-
-//           buffered, and the nine taps read their A fragments from it at a
-//           per-lane shifted row (taps outside the image read a zero row); K
-//           tiles chunk-major.  conv3_kernel's idea on byte rows.
-// The epilogue (F8Epi), fp32, in this order: v = fmaf(acc, a2[k], b[k]); v +=
-// s_res * float(res) (fp8, optional); ReLU; store q(v * inv_s_out) as fp8 or
-// bf16(v), q(v) = e4m3_rne(clamp(v, -448, 448)).
-#include <stdexcept>
+//           pixels of one tap (GatherA); K tiles tap-major;
+//   halo    3x3 / stride 1 / pad 1: the halo image of a 64-channel chunk
+//           (HaloA) is staged once, double-buffered, and the nine taps read
+//           their A fragments from it; K tiles chunk-major.  conv3_kernel's
+//           idea on byte rows.
+#include <type_traits>
 
-#include "common.h"
-#include "ops_generic.h"
+#include "lowp_conv_core.h"
 
 namespace gops {
 namespace cf8 {
 
-constexpr int BK = 64;     // bytes (channels) of a K tile row
-constexpr int PITCH = 80;  // LDS row pitch, bytes
-constexpr int BN = 64;
-constexpr int NT = 256;
-constexpr int HCAP = 248;  // halo rows an LDS image holds; row HCAP is all zeros
-constexpr int HLD = (HCAP + 63) / 64;  // halo 16-byte loads a thread
+using namespace lowp;
 
 typedef int i32x8 __attribute__((ext_vector_type(8)));
 
-// Built without the packed fp32 instructions (resnet_infer.hip says why).
-#define F8_TARGET __attribute__((target("no-packed-fp32-ops")))
-#define F8_KERNEL __global__ __launch_bounds__(NT) F8_TARGET
-#define F8_DEV __device__ __forceinline__ F8_TARGET
-
-// (HIP's header helpers - make_uint4, __syncthreads, __uint_as_float - carry the
-// default target features and would become real calls from these functions, so
-// the few that are needed are written on builtins here)
-F8_DEV uint4 zero4() {
-  uint4 z;
-  z.x = z.y = z.z = z.w = 0u;
-  return z;
-}
-F8_DEV uint4 keep4(uint4 v, bool ok) {
-  v.x = ok ? v.x : 0u, v.y = ok ? v.y : 0u, v.z = ok ? v.z : 0u, v.w = ok ? v.w : 0u;
-  return v;
-}
-F8_DEV void block_sync() {
-  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
-  __builtin_amdgcn_s_barrier();
-  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
-}
-F8_DEV float e4m3_to_f32(uint32_t byte) { return __builtin_amdgcn_cvt_f32_fp8((int)byte, 0); }
-// q(v): clamp in fp32, then the hardware's round-to-nearest-even convert
-F8_DEV uint32_t f32_to_e4m3(float v) {
-  v = fminf(fmaxf(v, -448.f), 448.f);
-  return (uint32_t)__builtin_amdgcn_cvt_pk_fp8_f32(v, 0.f, 0, false) & 0xffu;
-}
-
 // The operand tiles of K tile kt: load() issues the global loads into
 // registers, store() writes them into the LDS buffers tile kt is read from.
-// Every load is unconditional, from a pixel clamped into the tensor, and a
-// pixel outside the image is zeroed in registers (no branch around a load).
 // LDS: two A images of ASZ bytes, then two B tiles.
 template <int BM, bool HALO>
 struct Loader {
-  static constexpr int AR = BM / 64;
-  static constexpr int ASZ = (HALO ? HCAP + 1 : BM) * PITCH;
+  using A = std::conditional_t<HALO, HaloA<BM>, GatherA<BM>>;
+  static constexpr int ASZ = A::ASZ;
   static constexpr int BSZ = BN * PITCH;
-  const ConvShape s;
-  const uint8_t* x;
-  const uint8_t* wb;  // this thread's 16 bytes of B row lrow at (tap 0, channel 0)
-  int M, cpt, lrow, lc;
-  // gather: the input pixel of tap (0, 0) of this thread's AR rows
-  const uint8_t* xb[AR];
-  int iy0[AR], ix0[AR];
-  uint4 ra[AR];
-  // halo: the first pixel of the run, its rows
-  long long p0;
-  int hr;
-  uint4 rh[HALO ? HLD : 1];
-  uint4 rb;
+  A a;
+  const uint8_t* wb;  // this thread's 16 bytes of its B row at (tap 0, channel 0)
+  size_t wtap;        // bytes of a tap of B
+  int cpt, lo;        // chunks a tap; this thread's 16 bytes inside an LDS tile
+  u32x4 rb;           // (not a uint4: copied memory to memory, that one lives in scratch)
 
-  F8_DEV Loader(const ConvShape& s_, const uint8_t* x_, const uint8_t* wt, int m0, int n0)
-      : s(s_), x(x_) {
-    const int tid = threadIdx.x;
-    M = s.N * s.OH * s.OW, cpt = s.C / BK, lrow = tid >> 2, lc = (tid & 3) * 16;
+  LOWP_DEV Loader(const ConvShape& s, const uint8_t* x, const uint8_t* wt, int m0, int n0)
+      : a(s, x, m0) {
+    const int lrow = threadIdx.x >> 2, lc = (threadIdx.x & 3) * 16;
     wb = wt + (size_t)(n0 + lrow) * s.C + lc;
-    if constexpr (HALO) {
-      p0 = (long long)m0 - s.W - 1;
-      hr = BM + 2 * s.W + 2;
-    } else {
-#pragma unroll
-      for (int i = 0; i < AR; ++i) {
-        const int m = m0 + lrow + 64 * i;
-        if (m < M) {
-          const int ox = m % s.OW, t = m / s.OW, oy = t % s.OH, n = t / s.OH;
-          iy0[i] = oy * s.stride - s.pad, ix0[i] = ox * s.stride - s.pad;
-          xb[i] = x + (size_t)n * s.H * s.W * s.C + lc;
-        } else {  // a row past M: every tap is outside
-          iy0[i] = -(1 << 20), ix0[i] = 0, xb[i] = x;
-        }
-      }
-    }
+    wtap = (size_t)s.K * s.C, cpt = s.C / BK, lo = lrow * PITCH + lc;
   }
-  F8_DEV void load(int kt) {
-    int tap, c0;
+  LOWP_DEV void load(int kt) {
+    int tap, ch;
     if constexpr (HALO) {
-      const int chunk = kt / 9;
-      tap = kt - 9 * chunk, c0 = chunk * BK;
-      if (tap == 0) {
-#pragma unroll
-        for (int i = 0; i < HLD; ++i) {
-          const int j = lrow + 64 * i;
-          const long long p = p0 + j, pc = p < 0 ? 0 : (p < M ? p : M - 1);
-          rh[i] = keep4(*reinterpret_cast<const uint4*>(x + (size_t)pc * s.C + c0 + lc), p == pc);
-        }
-      }
+      ch = kt / 9, tap = kt - 9 * ch;
+      if (tap == 0) a.load(ch);
     } else {
-      tap = kt / cpt, c0 = (kt - tap * cpt) * BK;
-      const int kh = tap / s.S, kw = tap - kh * s.S;
-#pragma unroll
-      for (int i = 0; i < AR; ++i) {
-        const int iy = iy0[i] + kh, ix = ix0[i] + kw;
-        const int yc = min(max(iy, 0), s.H - 1), xc = min(max(ix, 0), s.W - 1);
-        ra[i] = keep4(*reinterpret_cast<const uint4*>(xb[i] + ((size_t)yc * s.W + xc) * s.C + c0),
-                      iy == yc && ix == xc);
-      }
+      tap = kt / cpt, ch = kt - tap * cpt;
+      a.load(ch, tap);
     }
-    rb = *reinterpret_cast<const uint4*>(wb + (size_t)tap * s.K * s.C + c0);
+    rb = *reinterpret_cast<const u32x4*>(wb + tap * wtap + ch * BK);
   }
-  F8_DEV void store(int kt, char* smem) const {
+  LOWP_DEV void store(int kt, char* smem) const {
     if constexpr (HALO) {
-      const int chunk = kt / 9;
-      if (kt - 9 * chunk == 0) {
-        char* A = smem + (chunk & 1) * ASZ;
-#pragma unroll
-        for (int i = 0; i < HLD; ++i) {
-          const int j = lrow + 64 * i;
-          if (j < hr) *reinterpret_cast<uint4*>(A + j * PITCH + lc) = rh[i];
-        }
-      }
+      if (kt % 9 == 0) a.store(smem + ((kt / 9) & 1) * ASZ);
     } else {
-      char* A = smem + (kt & 1) * ASZ;
-#pragma unroll
-      for (int i = 0; i < AR; ++i)
-        *reinterpret_cast<uint4*>(A + (lrow + 64 * i) * PITCH + lc) = ra[i];
+      a.store(smem + (kt & 1) * ASZ);
     }
-    *reinterpret_cast<uint4*>(smem + 2 * ASZ + (kt & 1) * BSZ + lrow * PITCH + lc) = rb;
+    *reinterpret_cast<u32x4*>(smem + 2 * ASZ + (kt & 1) * BSZ + lo) = rb;
   }
 };
 
 // one K tile of a 32 x 32 accumulator from the 32 bytes of this lane's A and B rows
 template <int MF>
-F8_DEV f32x16 mma_tile(const char* ap, const uint4 b0, const uint4 b1, f32x16 acc) {
+LOWP_DEV f32x16 mma_tile(const char* ap, const uint4 b0, const uint4 b1, f32x16 acc) {
   const uint4 a0 = *reinterpret_cast<const uint4*>(ap);
   const uint4 a1 = *reinterpret_cast<const uint4*>(ap + 16);
   if constexpr (MF == 1) {
@@ -207,43 +112,26 @@ F8_DEV f32x16 mma_tile(const char* ap, const uint4 b0, const uint4 b1, f32x16 ac
 }
 
 template <int BM, int MF, bool OUT8, bool HALO>
-F8_KERNEL void f8conv_kernel(const ConvShape s, const uint8_t* __restrict__ x,
-                             const uint8_t* __restrict__ wt, const F8Epi e, void* __restrict__ yv) {
+LOWP_KERNEL(NT) void f8conv_kernel(const ConvShape s, const uint8_t* __restrict__ x,
+                                   const uint8_t* __restrict__ wt, const F8Epi e,
+                                   void* __restrict__ yv) {
   using LD = Loader<BM, HALO>;
   constexpr int TM = BM / 64;
   constexpr int ASZ = LD::ASZ, BSZ = LD::BSZ;
   __shared__ __attribute__((aligned(16))) char smem[2 * ASZ + 2 * BSZ];
-  const int M = s.N * s.OH * s.OW;
-  const int mt = (M + BM - 1) / BM;
-  const int bid = xcd_remap(blockIdx.x, gridDim.x);
-  const int m0 = (bid % mt) * BM, n0 = (bid / mt) * BN;
+  const Tile<BM> t(s);
   const int nk = s.R * s.S * (s.C / BK);
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, wm = wave & 1, wn = wave >> 1;
-  const int r = lane & 31, h = lane >> 5;
-  LD ld(s, x, wt, m0, n0);
+  LD ld(s, x, wt, t.m0, t.n0);
   // the epilogue's per-column and per-conv operands, loaded before the main
   // loop (fwd_kernel: a load behind the first stores would wait for them)
-  const int co = n0 + wn * 32 + r;
-  const float fa = e.a2[co], fb = e.b[co];
+  const float fa = e.a2[t.co], fb = e.b[t.co];
   const float sres = e.res ? *e.s_res : 0.f;
   const float inv = OUT8 ? *e.inv_s_out : 1.f;
-  // halo: which of the nine taps of this lane's rows lie inside the image
   int mask[TM];
   if constexpr (HALO) {
-    if (tid < 2 * (PITCH / 16))  // the zero row of both images
-      *reinterpret_cast<uint4*>(smem + (tid / (PITCH / 16)) * ASZ + HCAP * PITCH +
-                                16 * (tid % (PITCH / 16))) = zero4();
+    zero_halo_rows(smem, ASZ, PITCH);
 #pragma unroll
-    for (int i = 0; i < TM; ++i) {
-      const int m = m0 + wm * (BM / 2) + 32 * i + r;
-      const int px = m % s.W, py = (m / s.W) % s.H;
-      mask[i] = 0;
-#pragma unroll
-      for (int t = 0; t < 9; ++t)
-        if (m < M && (unsigned)(py + t / 3 - 1) < (unsigned)s.H &&
-            (unsigned)(px + t % 3 - 1) < (unsigned)s.W)
-          mask[i] |= 1 << t;
-    }
+    for (int i = 0; i < TM; ++i) mask[i] = halo_mask(s, t.m0 + t.row(i), t.M);
   }
   f32x16 acc[TM];
 #pragma unroll
@@ -254,67 +142,40 @@ F8_KERNEL void f8conv_kernel(const ConvShape s, const uint8_t* __restrict__ x,
   for (int kt = 0; kt < nk; ++kt) {
     const bool more = kt + 1 < nk;
     if (more) ld.load(kt + 1);
-    const char* bp = smem + 2 * ASZ + (kt & 1) * BSZ + (wn * 32 + r) * PITCH + 32 * h;
+    const char* bp = smem + 2 * ASZ + (kt & 1) * BSZ + (t.wn * 32 + t.r) * PITCH + 32 * t.h;
     const uint4 b0 = *reinterpret_cast<const uint4*>(bp);
     const uint4 b1 = *reinterpret_cast<const uint4*>(bp + 16);
     if constexpr (HALO) {
       const int chunk = kt / 9, tap = kt - 9 * chunk;
       const int shift = (tap / 3) * s.W + tap % 3;
-      const char* A = smem + (chunk & 1) * ASZ + 32 * h;
+      const char* A = smem + (chunk & 1) * ASZ + 32 * t.h;
 #pragma unroll
       for (int i = 0; i < TM; ++i) {
-        const int row = (mask[i] >> tap) & 1 ? wm * (BM / 2) + 32 * i + r + shift : HCAP;
+        const int row = (mask[i] >> tap) & 1 ? t.row(i) + shift : HCAP;
         acc[i] = mma_tile<MF>(A + row * PITCH, b0, b1, acc[i]);
       }
     } else {
-      const char* A = smem + (kt & 1) * ASZ + 32 * h;
+      const char* A = smem + (kt & 1) * ASZ + 32 * t.h;
 #pragma unroll
-      for (int i = 0; i < TM; ++i)
-        acc[i] = mma_tile<MF>(A + (wm * (BM / 2) + 32 * i + r) * PITCH, b0, b1, acc[i]);
+      for (int i = 0; i < TM; ++i) acc[i] = mma_tile<MF>(A + t.row(i) * PITCH, b0, b1, acc[i]);
     }
     if (more) ld.store(kt + 1, smem);
     block_sync();
   }
-  // lane (r, h) holds column co of rows mb + (q & 3) + 8 (q >> 2); the residual
-  // loads first (rows clamped into the tensor), the stores last
-  const uint8_t* res = reinterpret_cast<const uint8_t*>(e.res);
-  const size_t K = s.K;
-#pragma unroll
-  for (int i = 0; i < TM; ++i) {
-    const int mb = m0 + wm * (BM / 2) + 32 * i + 4 * h;
-    float rv[16];
-#pragma unroll
-    for (int q = 0; q < 16; ++q) {
-      const int m = min(mb + (q & 3) + 8 * (q >> 2), M - 1);
-      rv[q] = res ? e4m3_to_f32(res[(size_t)m * K + co]) : 0.f;
-    }
-#pragma unroll
-    for (int q = 0; q < 16; ++q) {
-      const int m = mb + (q & 3) + 8 * (q >> 2);
-      float v = __builtin_fmaf(acc[i][q], fa, fb);
-      if (res) v += sres * rv[q];
-      if (e.relu) v = fmaxf(v, 0.f);
-      if (m >= M) continue;
-      if constexpr (OUT8)
-        reinterpret_cast<uint8_t*>(yv)[(size_t)m * K + co] = (uint8_t)f32_to_e4m3(v * inv);
-      else
-        reinterpret_cast<__bf16*>(yv)[(size_t)m * K + co] = (__bf16)v;
-    }
-  }
+  f8_epilogue<BM, OUT8>(acc, e, fa, fb, sres, inv, t, (size_t)s.K, yv);
 }
 
 // scale(amax) = 2^j, j the least integer with 448 2^j >= amax; scale(0) = 1.
 // Exact: amax = m 2^e with m in [0.5, 1) and 448 = 0.875 2^9, so j = e - 9 for
 // m <= 0.875, else e - 8.  j is held to [-100, 100] so that the scale and its
 // inverse are normal floats (docs/ACCURACY.md).
-F8_DEV int scale_exp(float amax) {
+LOWP_DEV int scale_exp(float amax) {
   if (!(amax > 0.f)) return 0;
   int ex;
   const float m = frexpf(amax, &ex);
   const int j = m <= 0.875f ? ex - 9 : ex - 8;
   return min(max(j, -100), 100);
 }
-F8_DEV float pow2(int j) { return __builtin_bit_cast(float, (uint32_t)(j + 127) << 23); }
 
 // Every conv's weights in ONE launch: jobs[j] = {w (HWIO fp32), out (fp8
 // [tap][k][c]), taps, C, K, offset into sw, first block, 0} (int64), K / 32
@@ -322,7 +183,8 @@ F8_DEV float pow2(int j) { return __builtin_bit_cast(float, (uint32_t)(j + 127) 
 // pass 1 takes max |w| over taps x C per channel (a max: no order dependence)
 // and writes sw[k] = scale(amax); pass 2 re-reads the slice 32 x 32 at a time
 // through an LDS transpose and writes the codes q(w / sw[k]), c contiguous.
-F8_KERNEL void wq_f8_kernel(const long long* __restrict__ jobs, int njobs, float* __restrict__ sw) {
+LOWP_KERNEL(NT) void wq_f8_kernel(const long long* __restrict__ jobs, int njobs,
+                                  float* __restrict__ sw) {
   __shared__ float t[32][33];
   __shared__ float red[8][32];
   __shared__ float inv_s[32];
@@ -370,10 +232,10 @@ F8_KERNEL void wq_f8_kernel(const long long* __restrict__ jobs, int njobs, float
 // scales are powers of two: exact), s_res and 1 / s_out into scal[j] and
 // scal[njobs + j]; block 0 also writes 1 / s of amax slot 0 (the pool output)
 // into scal[2 njobs].
-F8_KERNEL void f8_fold_kernel(const long long* __restrict__ jobs, int njobs,
-                              const float* __restrict__ fold, const float* __restrict__ sw,
-                              const float* __restrict__ amax, float* __restrict__ a2,
-                              float* __restrict__ scal) {
+LOWP_KERNEL(NT) void f8_fold_kernel(const long long* __restrict__ jobs, int njobs,
+                                    const float* __restrict__ fold, const float* __restrict__ sw,
+                                    const float* __restrict__ amax, float* __restrict__ a2,
+                                    float* __restrict__ scal) {
   const long long* J = jobs + 8 * blockIdx.x;
   const int off = (int)J[0], K = (int)J[1], in = (int)J[2], out = (int)J[3], rs = (int)J[4];
   const float s_in = pow2(scale_exp(amax[in]));
@@ -388,8 +250,7 @@ F8_KERNEL void f8_fold_kernel(const long long* __restrict__ jobs, int njobs,
 template <int BM, int MF, bool HALO>
 static void launch(const ConvShape& s, const void* x, const void* w, const F8Epi& e, void* y,
                    bool out_bf16, hipStream_t st) {
-  const int M = s.N * s.OH * s.OW;
-  const dim3 grid((unsigned)(((M + BM - 1) / BM) * (s.K / BN)));
+  const dim3 grid = conv_grid(s, BM);
   const uint8_t* x8 = reinterpret_cast<const uint8_t*>(x);
   const uint8_t* w8 = reinterpret_cast<const uint8_t*>(w);
   if (out_bf16)
@@ -403,15 +264,7 @@ static void launch(const ConvShape& s, const void* x, const void* w, const F8Epi
 static int g_mfma = 1;  // the MFMA form of mfma = 0 (f8conv_set_mfma)
 static int g_form = 2;  // the loader of form = 0 where the halo loader applies (f8conv_set_form)
 
-#undef F8_KERNEL
-#undef F8_DEV
-#undef F8_TARGET
-
 }  // namespace cf8
-
-static bool f8_halo_ok(const ConvShape& s, int bm) {
-  return s.R == 3 && s.S == 3 && s.stride == 1 && s.pad == 1 && bm + 2 * s.W + 2 <= cf8::HCAP;
-}
 
 bool f8conv_ok(const ConvShape& s) {
   const long long M = (long long)s.N * s.OH * s.OW;
@@ -422,19 +275,9 @@ bool f8conv_ok(const ConvShape& s) {
          M + 128 < (1LL << 31) && (long long)s.N * s.H * s.W < (1LL << 31);
 }
 
+// (docs/PERF_NOTES.md holds the measurements behind g_form)
 F8Plan f8conv_plan(const ConvShape& s, int form) {
-  if (!f8conv_ok(s)) throw std::runtime_error("f8conv: unsupported shape");
-  if (form < 0 || form > 2) throw std::runtime_error("f8conv: form must be 0, 1 (gather) or 2 (halo)");
-  F8Plan p;
-  const long long M = (long long)s.N * s.OH * s.OW;
-  // 128-row tiles once they alone give every CU (256) a block
-  p.bm = (M / 128) * (s.K / 64) >= 256 ? 128 : 64;
-  // the planner's choice (docs/PERF_NOTES.md holds the measurements behind g_form)
-  p.form = form == 0 ? (cf8::g_form == 2 && f8_halo_ok(s, p.bm) ? 2 : 1) : form;
-  if (p.form == 2 && !f8_halo_ok(s, p.bm))
-    throw std::runtime_error("f8conv: the halo form takes 3x3 / stride 1 / pad 1 with "
-                             "bm + 2 W + 2 <= 248");
-  return p;
+  return lowp::byte_conv_plan(s, form, cf8::g_form, "f8conv");
 }
 
 void f8conv_set_mfma(int mf) {

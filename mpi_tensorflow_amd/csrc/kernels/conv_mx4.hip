@@ -3,10 +3,10 @@
 // (docs/ACCURACY.md "ResNet-18 mxfp4 inference"), and the weight quantiser that
 // feeds it.
 //
-// conv_f8.hip's geometry (256 threads, 2 x 2 waves, block tiles 128 x 64 and
-// 64 x 64 by f8conv's rule, one 32 x 32 accumulator per 32 rows of a wave, no
-// split-K, no atomics, one fixed accumulation order, XCD-aware block order) and
-// its epilogue (F8Epi); the B operand and the K loop are this file's own.
+// lowp_conv_core.h's geometry (256 threads, 2 x 2 waves, block tiles 128 x 64
+// and 64 x 64 by byte_conv_plan's rule, no split-K, no atomics), its A loaders
+// (HaloA, GatherA) and its epilogue (F8Epi), all shared with conv_f8.hip; the B
+// operand and the K loop are this file's own.
 //
 // MFMA.  One v_mfma_scale_f32_32x32x64_f8f6f4 per 32 x 32 tile per (tap,
 // 64-channel chunk): cbsz = 0, A is e4m3, block scale 2^0; blgp = 4, B is
@@ -35,79 +35,43 @@
 // and has no bank conflicts; its scale read is 64 contiguous bytes.
 //
 // K loop, chunk-major in both forms (template flag HALO):
-//   halo    3x3 / stride 1 / pad 1 (f8conv's condition): A is f8conv's halo
-//           image (pitch 80, a zero row, per-lane tap masks), double-buffered;
+//   halo    3x3 / stride 1 / pad 1 (halo_ok): A is the core's halo image
+//           (pitch 80, a zero row, per-lane tap masks), double-buffered;
 //           the 9-tap slab (19,584 bytes) is single-buffered.  Per chunk the
 //           next chunk's halo and slab loads are issued into registers, the
 //           nine taps run back to back from LDS with no barrier between them,
 //           then the halo registers go to the other image, a barrier, the slab
 //           registers over the slab, a barrier: two barriers a chunk where
 //           f8conv takes nine.  LDS 39,840 + 19,584 bytes (static).
-//   gather  R in {1, 3}, stride in {1, 2}: f8conv's per-tap gathered A tile,
+//   gather  R in {1, 3}, stride in {1, 2}: the core's per-tap gathered A tile,
 //           double-buffered, one barrier a tap; A tiles are small here, so the
 //           slab is double-buffered too (20,480 + 39,168 bytes at BM = 128) and
 //           a 1x1 conv keeps one barrier a K tile.
-#include <stdexcept>
-
-#include "common.h"
-#include "ops_generic.h"
+#include "lowp_conv_core.h"
 
 namespace gops {
 namespace cmx4 {
 
-constexpr int BK = 64;     // channels (bytes of A) of a K tile row
-constexpr int PITCH = 80;  // LDS row pitch of A, bytes (conv_f8.hip says why)
-constexpr int BN = 64;
-constexpr int NT = 256;
-constexpr int HCAP = 248;  // halo rows an LDS image holds; row HCAP is all zeros
-constexpr int HLD = (HCAP + 63) / 64;  // halo 16-byte loads a thread
-constexpr int TAPB = 2048 + 128;       // slab bytes a tap: codes, scales
+using namespace lowp;
+
+constexpr int TAPB = 2048 + 128;  // slab bytes a tap: codes, scales
 constexpr int SLAB9 = 9 * TAPB;
 constexpr int SLD = (SLAB9 / 16 + NT - 1) / NT;  // slab 16-byte loads a thread
 
 typedef int i32x8 __attribute__((ext_vector_type(8)));
-typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
-
-// Built without the packed fp32 instructions (resnet_infer.hip says why).
-#define MX_TARGET __attribute__((target("no-packed-fp32-ops")))
-// (two waves a SIMD: the two blocks a CU's LDS holds)
-#define MX_KERNEL __global__ __launch_bounds__(NT, 2) MX_TARGET
-#define MX_DEV __device__ __forceinline__ MX_TARGET
-
-// (as in conv_f8.hip: HIP's header helpers carry the default target features,
-// so the few that are needed are written on builtins)
-MX_DEV uint4 zero4() {
-  uint4 z;
-  z.x = z.y = z.z = z.w = 0u;
-  return z;
-}
-MX_DEV uint4 keep4(uint4 v, bool ok) {
-  v.x = ok ? v.x : 0u, v.y = ok ? v.y : 0u, v.z = ok ? v.z : 0u, v.w = ok ? v.w : 0u;
-  return v;
-}
-MX_DEV void block_sync() {
-  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
-  __builtin_amdgcn_s_barrier();
-  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
-}
-MX_DEV float e4m3_to_f32(uint32_t byte) { return __builtin_amdgcn_cvt_f32_fp8((int)byte, 0); }
-MX_DEV uint32_t f32_to_e4m3(float v) {
-  v = fminf(fmaxf(v, -448.f), 448.f);
-  return (uint32_t)__builtin_amdgcn_cvt_pk_fp8_f32(v, 0.f, 0, false) & 0xffu;
-}
 
 // The slab of one chunk: load() issues this thread's 16-byte global loads,
 // store() writes them to an LDS slab.  n16 = taps * 136 vectors.
 struct Slab {
   u32x4 rs[SLD];
-  MX_DEV void load(const uint8_t* g, int n16) {
+  LOWP_DEV void load(const uint8_t* g, int n16) {
 #pragma unroll
     for (int i = 0; i < SLD; ++i) {
       const int j = threadIdx.x + NT * i;
       rs[i] = reinterpret_cast<const u32x4*>(g)[j < n16 ? j : 0];
     }
   }
-  MX_DEV void store(char* lds, int n16) const {
+  LOWP_DEV void store(char* lds, int n16) const {
 #pragma unroll
     for (int i = 0; i < SLD; ++i) {
       const int j = threadIdx.x + NT * i;
@@ -116,82 +80,9 @@ struct Slab {
   }
 };
 
-// f8conv's halo image of one 64-channel chunk: the run of input pixels from one
-// image row above the block's output pixels to one below, clamped into the
-// tensor, zeros outside it.  load() issues the global loads into registers,
-// store() writes them into image ch & 1.
-template <int BM>
-struct HaloA {
-  const uint8_t* x;
-  long long p0;
-  int M, C, hr, lrow, lc;
-  uint4 rh[HLD];
-  MX_DEV HaloA(const ConvShape& s, const uint8_t* x_, int m0) : x(x_) {
-    M = s.N * s.OH * s.OW, C = s.C, lrow = threadIdx.x >> 2, lc = (threadIdx.x & 3) * 16;
-    p0 = (long long)m0 - s.W - 1, hr = BM + 2 * s.W + 2;
-  }
-  MX_DEV void load(int ch) {
-#pragma unroll
-    for (int i = 0; i < HLD; ++i) {
-      const long long p = p0 + lrow + 64 * i, pc = p < 0 ? 0 : (p < M ? p : M - 1);
-      rh[i] = keep4(*reinterpret_cast<const uint4*>(x + (size_t)pc * C + ch * BK + lc), p == pc);
-    }
-  }
-  MX_DEV void store(char* A) const {
-#pragma unroll
-    for (int i = 0; i < HLD; ++i) {
-      const int j = lrow + 64 * i;
-      if (j < hr) *reinterpret_cast<uint4*>(A + j * PITCH + lc) = rh[i];
-    }
-  }
-};
-
-// f8conv's gathered A tile of one (chunk, tap): BM input pixels of the tap.
-// Every load is unconditional, from a pixel clamped into the tensor, and a
-// pixel outside the image is zeroed in registers.
-template <int BM>
-struct GatherA {
-  static constexpr int AR = BM / 64;
-  const ConvShape s;
-  int lrow, lc;
-  const uint8_t* xb[AR];  // the input pixel of tap (0, 0) of this thread's AR rows
-  int iy0[AR], ix0[AR];
-  uint4 ra[AR];
-  MX_DEV GatherA(const ConvShape& s_, const uint8_t* x, int m0) : s(s_) {
-    const int M = s.N * s.OH * s.OW;
-    lrow = threadIdx.x >> 2, lc = (threadIdx.x & 3) * 16;
-#pragma unroll
-    for (int i = 0; i < AR; ++i) {
-      const int m = m0 + lrow + 64 * i;
-      if (m < M) {
-        const int ox = m % s.OW, t = m / s.OW, oy = t % s.OH, n = t / s.OH;
-        iy0[i] = oy * s.stride - s.pad, ix0[i] = ox * s.stride - s.pad;
-        xb[i] = x + (size_t)n * s.H * s.W * s.C + lc;
-      } else {  // a row past M: every tap is outside
-        iy0[i] = -(1 << 20), ix0[i] = 0, xb[i] = x;
-      }
-    }
-  }
-  MX_DEV void load(int ch, int tap) {
-    const int kh = tap / s.S, kw = tap - kh * s.S;
-#pragma unroll
-    for (int i = 0; i < AR; ++i) {
-      const int iy = iy0[i] + kh, ix = ix0[i] + kw;
-      const int yc = min(max(iy, 0), s.H - 1), xc = min(max(ix, 0), s.W - 1);
-      ra[i] = keep4(*reinterpret_cast<const uint4*>(xb[i] + ((size_t)yc * s.W + xc) * s.C + ch * BK),
-                    iy == yc && ix == xc);
-    }
-  }
-  MX_DEV void store(char* A) const {
-#pragma unroll
-    for (int i = 0; i < AR; ++i)
-      *reinterpret_cast<uint4*>(A + (lrow + 64 * i) * PITCH + lc) = ra[i];
-  }
-};
-
 // one (tap, chunk) of a 32 x 32 accumulator: the lane's two 16-byte runs of A
 // (ap = its row + 16 h), its 16 bytes of B codes and its block scale
-MX_DEV f32x16 mma_tile(const char* ap, const uint4 b, int scale, f32x16 acc) {
+LOWP_DEV f32x16 mma_tile(const char* ap, const uint4 b, int scale, f32x16 acc) {
   const uint4 a0 = *reinterpret_cast<const uint4*>(ap);
   const uint4 a1 = *reinterpret_cast<const uint4*>(ap + 32);
   const i32x8 av = {(int)a0.x, (int)a0.y, (int)a0.z, (int)a0.w,
@@ -201,58 +92,25 @@ MX_DEV f32x16 mma_tile(const char* ap, const uint4 b, int scale, f32x16 acc) {
   return __builtin_amdgcn_mfma_scale_f32_32x32x64_f8f6f4(av, bv, acc, 0, 4, 0, 0x7f7f7f7f, 0, scale);
 }
 
-// F8Epi on the accumulators: lane (r, h) holds column co of rows mb + (q & 3)
-// + 8 (q >> 2); the residual loads first (rows clamped into the tensor), the
-// stores last
-template <int TM, bool OUT8>
-MX_DEV void epilogue(const f32x16 (&acc)[TM], const F8Epi& e, float fa, float fb, float sres,
-                     float inv, int mrow, int M, int co, size_t K, void* yv) {
-  const uint8_t* res = reinterpret_cast<const uint8_t*>(e.res);
-#pragma unroll
-  for (int i = 0; i < TM; ++i) {
-    const int mb = mrow + 32 * i;
-    float rv[16];
-#pragma unroll
-    for (int q = 0; q < 16; ++q) {
-      const int m = min(mb + (q & 3) + 8 * (q >> 2), M - 1);
-      rv[q] = res ? e4m3_to_f32(res[(size_t)m * K + co]) : 0.f;
-    }
-#pragma unroll
-    for (int q = 0; q < 16; ++q) {
-      const int m = mb + (q & 3) + 8 * (q >> 2);
-      float v = __builtin_fmaf(acc[i][q], fa, fb);
-      if (res) v += sres * rv[q];
-      if (e.relu) v = fmaxf(v, 0.f);
-      if (m >= M) continue;
-      if constexpr (OUT8)
-        reinterpret_cast<uint8_t*>(yv)[(size_t)m * K + co] = (uint8_t)f32_to_e4m3(v * inv);
-      else
-        reinterpret_cast<__bf16*>(yv)[(size_t)m * K + co] = (__bf16)v;
-    }
-  }
-}
-
+// (two waves a SIMD: the two blocks a CU's LDS holds)
 template <int BM, bool OUT8, bool HALO>
-MX_KERNEL void mx4conv_kernel(const ConvShape s, const uint8_t* __restrict__ x,
-                              const uint8_t* __restrict__ wt, const F8Epi e, void* __restrict__ yv) {
+LOWP_KERNEL(NT, 2) void mx4conv_kernel(const ConvShape s, const uint8_t* __restrict__ x,
+                                       const uint8_t* __restrict__ wt, const F8Epi e,
+                                       void* __restrict__ yv) {
   constexpr int TM = BM / 64;
-  constexpr int ASZ = (HALO ? HCAP + 1 : BM) * PITCH;
+  constexpr int ASZ = HALO ? HaloA<BM>::ASZ : GatherA<BM>::ASZ;
   __shared__ __attribute__((aligned(16))) char smem[2 * ASZ + (HALO ? 1 : 2) * SLAB9];
   char* const sl = smem + 2 * ASZ;
-  const int M = s.N * s.OH * s.OW;
-  const int mt = (M + BM - 1) / BM;
-  const int bid = xcd_remap(blockIdx.x, gridDim.x);
-  const int m0 = (bid % mt) * BM, n0 = (bid / mt) * BN;
+  const Tile<BM> t(s);
   const int taps = s.R * s.S, nch = s.C / BK;
   const int n16 = taps * (TAPB / 16);
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, wm = wave & 1, wn = wave >> 1;
-  const int r = lane & 31, h = lane >> 5;
+  const int lane = threadIdx.x & 63, h = t.h;
   // this block's slabs: chunk ch at ws + ch * taps * TAPB
-  const uint8_t* ws = wt + (size_t)(n0 / BN) * nch * taps * TAPB;
+  const uint8_t* ws = wt + (size_t)(t.n0 / BN) * nch * taps * TAPB;
   // this lane's B codes and scale byte of tap 0 inside a slab
-  const int bo = wn * 1024 + lane * 16, so = taps * 2048 + wn * 64 + lane;
-  const int co = n0 + wn * 32 + r;
-  const float fa = e.a2[co], fb = e.b[co];
+  const int bo = t.wn * 1024 + lane * 16, so = taps * 2048 + t.wn * 64 + lane;
+  // the epilogue's operands, loaded before the main loop
+  const float fa = e.a2[t.co], fb = e.b[t.co];
   const float sres = e.res ? *e.s_res : 0.f;
   const float inv = OUT8 ? *e.inv_s_out : 1.f;
   f32x16 acc[TM];
@@ -260,23 +118,11 @@ MX_KERNEL void mx4conv_kernel(const ConvShape s, const uint8_t* __restrict__ x,
   for (int i = 0; i < TM; ++i) acc[i] = zero16();
   Slab sb;
   if constexpr (HALO) {
-    if (tid < 2 * (PITCH / 16))  // the zero row of both images
-      *reinterpret_cast<uint4*>(smem + (tid / (PITCH / 16)) * ASZ + HCAP * PITCH +
-                                16 * (tid % (PITCH / 16))) = zero4();
-    // which of the nine taps of this lane's rows lie inside the image
+    zero_halo_rows(smem, ASZ, PITCH);
     int mask[TM];
 #pragma unroll
-    for (int i = 0; i < TM; ++i) {
-      const int m = m0 + wm * (BM / 2) + 32 * i + r;
-      const int px = m % s.W, py = (m / s.W) % s.H;
-      mask[i] = 0;
-#pragma unroll
-      for (int t = 0; t < 9; ++t)
-        if (m < M && (unsigned)(py + t / 3 - 1) < (unsigned)s.H &&
-            (unsigned)(px + t % 3 - 1) < (unsigned)s.W)
-          mask[i] |= 1 << t;
-    }
-    HaloA<BM> ha(s, x, m0);
+    for (int i = 0; i < TM; ++i) mask[i] = halo_mask(s, t.m0 + t.row(i), t.M);
+    HaloA<BM> ha(s, x, t.m0);
     ha.load(0);
     sb.load(ws, n16);
     ha.store(smem);
@@ -301,7 +147,7 @@ MX_KERNEL void mx4conv_kernel(const ConvShape s, const uint8_t* __restrict__ x,
           const int shift = kh * s.W + kw;
 #pragma unroll
           for (int i = 0; i < TM; ++i) {
-            const int row = (mask[i] >> tap) & 1 ? wm * (BM / 2) + 32 * i + r + shift : HCAP;
+            const int row = (mask[i] >> tap) & 1 ? t.row(i) + shift : HCAP;
             acc[i] = mma_tile(A + row * PITCH, b, sc, acc[i]);
           }
         }
@@ -314,7 +160,7 @@ MX_KERNEL void mx4conv_kernel(const ConvShape s, const uint8_t* __restrict__ x,
       }
     }
   } else {
-    GatherA<BM> ga(s, x, m0);
+    GatherA<BM> ga(s, x, t.m0);
     const size_t slab = (size_t)taps * TAPB;
     ga.load(0, 0);
     sb.load(ws, n16);
@@ -332,8 +178,7 @@ MX_KERNEL void mx4conv_kernel(const ConvShape s, const uint8_t* __restrict__ x,
         const int sc = *reinterpret_cast<const uint8_t*>(S0 + tap * 128 + so);
         const char* A = smem + (kt & 1) * ASZ + 16 * h;
 #pragma unroll
-        for (int i = 0; i < TM; ++i)
-          acc[i] = mma_tile(A + (wm * (BM / 2) + 32 * i + r) * PITCH, b, sc, acc[i]);
+        for (int i = 0; i < TM; ++i) acc[i] = mma_tile(A + t.row(i) * PITCH, b, sc, acc[i]);
         if (more) ga.store(smem + ((kt + 1) & 1) * ASZ);
         // the other slab: its readers passed the barrier that ended chunk ch - 1
         if (last && more) sb.store(sl + ((ch + 1) & 1) * SLAB9, n16);
@@ -341,15 +186,13 @@ MX_KERNEL void mx4conv_kernel(const ConvShape s, const uint8_t* __restrict__ x,
       }
     }
   }
-  epilogue<TM, OUT8>(acc, e, fa, fb, sres, inv, m0 + wm * (BM / 2) + 4 * h, M, co, (size_t)s.K, yv);
+  f8_epilogue<BM, OUT8>(acc, e, fa, fb, sres, inv, t, (size_t)s.K, yv);
 }
-
-MX_DEV float pow2(int j) { return __builtin_bit_cast(float, (uint32_t)(j + 127) << 23); }
 
 // E of a block: the least integer with 6 2^E >= amax, 0 for an all-zero block,
 // held to [-100, 100].  Exact: amax = m 2^e with m in [0.5, 1) and 6 = 0.75
 // 2^3, so E = e - 3 for m <= 0.75, else e - 2.
-MX_DEV int block_exp(float amax) {
+LOWP_DEV int block_exp(float amax) {
   if (!(amax > 0.f)) return 0;
   int ex;
   const float m = frexpf(amax, &ex);
@@ -358,7 +201,7 @@ MX_DEV int block_exp(float amax) {
 
 // e2m1 code of v = w 2^-E (exact): the nearest of {0, .5, 1, 1.5, 2, 3, 4, 6},
 // a tie to the even 3-bit magnitude index; w's sign in bit 3
-MX_DEV uint32_t e2m1(float w, float inv) {
+LOWP_DEV uint32_t e2m1(float w, float inv) {
   const float a = fabsf(w) * inv;
   const uint32_t idx = (a > 0.25f) + (a >= 0.75f) + (a > 1.25f) + (a >= 1.75f) + (a > 2.5f) +
                        (a >= 3.5f) + (a > 5.f);
@@ -371,7 +214,7 @@ MX_DEV uint32_t e2m1(float w, float inv) {
 // (tap, h, k) = the 32 channels 64 ch + 32 h + [0, 32) of output channel k of
 // the tile; the 64 threads of a wave read 64 consecutive k (256 bytes a
 // channel).  The block's amax is a max over its 32 values: no order dependence.
-MX_KERNEL void wq_mx4_kernel(const long long* __restrict__ jobs, int njobs) {
+LOWP_KERNEL(NT, 2) void wq_mx4_kernel(const long long* __restrict__ jobs, int njobs) {
   const int b = blockIdx.x;
   int j = 0;
   for (int i = 1; i < njobs; ++i)
@@ -408,8 +251,7 @@ MX_KERNEL void wq_mx4_kernel(const long long* __restrict__ jobs, int njobs) {
 template <int BM, bool HALO>
 static void launch(const ConvShape& s, const void* x, const void* w, const F8Epi& e, void* y,
                    bool out_bf16, hipStream_t st) {
-  const int M = s.N * s.OH * s.OW;
-  const dim3 grid((unsigned)(((M + BM - 1) / BM) * (s.K / BN)));
+  const dim3 grid = conv_grid(s, BM);
   const uint8_t* x8 = reinterpret_cast<const uint8_t*>(x);
   const uint8_t* w8 = reinterpret_cast<const uint8_t*>(w);
   if (out_bf16)
@@ -418,25 +260,11 @@ static void launch(const ConvShape& s, const void* x, const void* w, const F8Epi
     mx4conv_kernel<BM, true, HALO><<<grid, NT, 0, st>>>(s, x8, w8, e, y);
 }
 
-#undef MX_KERNEL
-#undef MX_DEV
-#undef MX_TARGET
-
 }  // namespace cmx4
 
+// form 0: the halo form wherever it applies
 F8Plan mx4conv_plan(const ConvShape& s, int form) {
-  if (!f8conv_ok(s)) throw std::runtime_error("mx4conv: unsupported shape");
-  if (form < 0 || form > 2) throw std::runtime_error("mx4conv: form must be 0, 1 (gather) or 2 (halo)");
-  F8Plan p;
-  const long long M = (long long)s.N * s.OH * s.OW;
-  p.bm = (M / 128) * (s.K / 64) >= 256 ? 128 : 64;  // f8conv's rule
-  const bool halo_ok = s.R == 3 && s.S == 3 && s.stride == 1 && s.pad == 1 &&
-                       p.bm + 2 * s.W + 2 <= cmx4::HCAP;
-  p.form = form == 0 ? (halo_ok ? 2 : 1) : form;
-  if (p.form == 2 && !halo_ok)
-    throw std::runtime_error("mx4conv: the halo form takes 3x3 / stride 1 / pad 1 with "
-                             "bm + 2 W + 2 <= 248");
-  return p;
+  return lowp::byte_conv_plan(s, form, 2, "mx4conv");
 }
 
 void mx4conv(const ConvShape& s, const void* x, const void* w, const F8Epi& e, void* y,

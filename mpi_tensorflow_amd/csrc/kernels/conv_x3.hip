@@ -12,9 +12,12 @@
 // where v_mfma_f32_32x32x2_f32 runs at a sixteenth.
 //
 // x3conv_kernel:
-//   * 256 threads, 2 x 2 waves; block tiles 128 x 64 and 64 x 64 (x3conv_plan,
-//     by M), one 32 x 32 accumulator per 32 rows of a wave, fwd_kernel's
-//     XCD-aware block order;
+//   * lowp_conv_core.h's geometry (256 threads, 2 x 2 waves, block tiles 128 x
+//     64 and 64 x 64 - x3conv_plan, by M - no split-K, no atomics) and its halo
+//     mask and zero row; the loaders are this file's own (32-row passes, two
+//     planes, the swizzle, the stem), and so are the kernel's block and lane
+//     coordinates (docs/PERF_NOTES.md: with the core's Tile the halo form
+//     measured 0.7 % slower);
 //   * a K tile is one tap x 32 channels = ONE 128-byte LDS row per pixel (A) and
 //     per output channel (B): 16-byte pieces 0-3 are the 32 hi channels, pieces
 //     4-7 the 32 lo channels.  The loaders fetch piece p of a row from plane
@@ -39,11 +42,8 @@
 //     ds_write_b128 (2 rows x 8 pieces a 16-lane group) fill the 16 units once
 //     too.  No padding: an LDS row is exactly the 128 bytes it carries;
 //   * 16-byte global loads through registers, double-buffered LDS, the next
-//     tile's loads in flight during this tile's MFMAs, one barrier a K tile;
-//   * NO split-K and no atomics: one wave accumulates an output element over
-//     the K tiles in one fixed order, so a row's result does not depend on the
-//     rows that share its launch (a small chunk fills few CUs on layer 4; that
-//     is accepted, as in f8conv).
+//     tile's loads in flight during this tile's MFMAs, one barrier a K tile (a
+//     small chunk fills few CUs on layer 4; that is accepted).
 // Three loaders (template MODE):
 //   gather  R in {1, 3}, stride in {1, 2}: each K tile gathers its BM input
 //           pixels of one tap (zeros outside the image); K tiles tap-major;
@@ -63,53 +63,28 @@
 //           8 K tiles.  LDS as gather.
 // The epilogue (X3Epi), fp32, in this order: v = fmaf(acc, a[k], b[k]); v +=
 // hi + lo of res[m][k] (optional); ReLU; store split(v) into the two planes.
-#include <stdexcept>
-
-#include "common.h"
-#include "ops_generic.h"
+#include "lowp_conv_core.h"
 
 namespace gops {
 namespace cx3 {
 
+using namespace lowp;
+
 constexpr int ROW = 128;  // bytes of an LDS row: 32 hi + 32 lo channels
-constexpr int BN = 64;
-constexpr int NT = 256;
-constexpr int HCAP = 248;  // halo rows an LDS image holds; row HCAP is all zeros
 constexpr int HLD = (HCAP + 31) / 32;  // halo 16-byte loads a thread
 enum { GATHER = 0, HALO = 1, STEM = 2 };
 
 typedef __bf16 bf16v8 __attribute__((ext_vector_type(8)));
 
-// Built without the packed fp32 instructions (resnet_infer.hip says why).
-#define X3_TARGET __attribute__((target("no-packed-fp32-ops")))
-#define X3_KERNEL __global__ __launch_bounds__(NT) X3_TARGET
-#define X3_DEV __device__ __forceinline__ X3_TARGET
-
-// (HIP's header helpers carry the default target features and would become real
-// calls from these functions, so the few that are needed are written here)
-X3_DEV uint4 zero4() {
-  uint4 z;
-  z.x = z.y = z.z = z.w = 0u;
-  return z;
-}
-X3_DEV uint4 keep4(uint4 v, bool ok) {
-  v.x = ok ? v.x : 0u, v.y = ok ? v.y : 0u, v.z = ok ? v.z : 0u, v.w = ok ? v.w : 0u;
-  return v;
-}
-X3_DEV void block_sync() {
-  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
-  __builtin_amdgcn_s_barrier();
-  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
-}
-X3_DEV float bf_f32(uint32_t bits) { return __builtin_bit_cast(float, bits << 16); }
+LOWP_DEV float bf_f32(uint32_t bits) { return __builtin_bit_cast(float, bits << 16); }
 // split(v): the bits of hi = bf16_rne(v) and of lo = bf16_rne(v - hi)
-X3_DEV void split(float v, uint32_t& hi, uint32_t& lo) {
+LOWP_DEV void split(float v, uint32_t& hi, uint32_t& lo) {
   const __bf16 h = (__bf16)v;
   const __bf16 l = (__bf16)(v - (float)h);
   hi = __builtin_bit_cast(uint16_t, h), lo = __builtin_bit_cast(uint16_t, l);
 }
 // byte offset of piece p of LDS row j
-X3_DEV int slot(int j, int p) { return j * ROW + 16 * (p ^ ((j >> 1) & 7)); }
+LOWP_DEV int slot(int j, int p) { return j * ROW + 16 * (p ^ ((j >> 1) & 7)); }
 
 // The operand tiles of K tile kt: load() issues the global loads into
 // registers, store() writes them into the LDS buffers tile kt is read from.
@@ -135,7 +110,7 @@ struct Loader {
   uint4 rh[MODE == HALO ? HLD : 1];
   uint4 rb[2];
 
-  X3_DEV Loader(const ConvShape& s_, const uint16_t* x, const uint16_t* wt, int m0, int n0)
+  LOWP_DEV Loader(const ConvShape& s_, const uint16_t* x, const uint16_t* wt, int m0, int n0)
       : s(s_) {
     const int tid = threadIdx.x;
     M = s.N * s.OH * s.OW, cpt = s.C / 32, lrow = tid >> 3, pc = tid & 7;
@@ -165,7 +140,7 @@ struct Loader {
       }
     }
   }
-  X3_DEV void load(int kt) {
+  LOWP_DEV void load(int kt) {
     size_t wo;
     if constexpr (MODE == HALO) {
       const int chunk = kt / 9, tap = kt - 9 * chunk, c0 = chunk * 32;
@@ -197,7 +172,7 @@ struct Loader {
     rb[0] = *reinterpret_cast<const uint4*>(wb[0] + wo);
     rb[1] = *reinterpret_cast<const uint4*>(wb[1] + wo);
   }
-  X3_DEV void store(int kt, char* smem) const {
+  LOWP_DEV void store(int kt, char* smem) const {
     if constexpr (MODE == HALO) {
       const int chunk = kt / 9;
       if (kt - 9 * chunk == 0) {
@@ -223,7 +198,7 @@ struct Loader {
 struct Frag {
   bf16v8 hi[2], lo[2];
 };
-X3_DEV Frag frag(const char* base, int j, int h) {
+LOWP_DEV Frag frag(const char* base, int j, int h) {
   Frag f;
 #pragma unroll
   for (int c = 0; c < 2; ++c) {
@@ -234,7 +209,7 @@ X3_DEV Frag frag(const char* base, int j, int h) {
   return f;
 }
 // one K tile of a 32 x 32 accumulator: per K step (Ah, Bh), (Ah, Bl), (Al, Bh)
-X3_DEV f32x16 mma_tile(const Frag& a, const Frag& b, f32x16 acc) {
+LOWP_DEV f32x16 mma_tile(const Frag& a, const Frag& b, f32x16 acc) {
 #pragma unroll
   for (int c = 0; c < 2; ++c) {
     acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a.hi[c], b.hi[c], acc, 0, 0, 0);
@@ -245,9 +220,9 @@ X3_DEV f32x16 mma_tile(const Frag& a, const Frag& b, f32x16 acc) {
 }
 
 template <int BM, int MODE>
-X3_KERNEL void x3conv_kernel(const ConvShape s, const uint16_t* __restrict__ x,
-                             const uint16_t* __restrict__ wt, const X3Epi e,
-                             uint16_t* __restrict__ y) {
+LOWP_KERNEL(NT) void x3conv_kernel(const ConvShape s, const uint16_t* __restrict__ x,
+                                   const uint16_t* __restrict__ wt, const X3Epi e,
+                                   uint16_t* __restrict__ y) {
   using LD = Loader<BM, MODE>;
   constexpr int TM = BM / 64;
   constexpr int ASZ = LD::ASZ, BSZ = LD::BSZ;
@@ -264,23 +239,11 @@ X3_KERNEL void x3conv_kernel(const ConvShape s, const uint16_t* __restrict__ x,
   // (fwd_kernel: a load behind the first stores would wait for them)
   const int co = n0 + wn * 32 + r;
   const float fa = e.a[co], fb = e.b[co];
-  // halo: which of the nine taps of this lane's rows lie inside the image
   int mask[TM];
   if constexpr (MODE == HALO) {
-    if (tid < 2 * (ROW / 16))  // the zero row of both images
-      *reinterpret_cast<uint4*>(smem + (tid / (ROW / 16)) * ASZ + HCAP * ROW +
-                                16 * (tid % (ROW / 16))) = zero4();
+    zero_halo_rows(smem, ASZ, ROW);
 #pragma unroll
-    for (int i = 0; i < TM; ++i) {
-      const int m = m0 + wm * (BM / 2) + 32 * i + r;
-      const int px = m % s.W, py = (m / s.W) % s.H;
-      mask[i] = 0;
-#pragma unroll
-      for (int t = 0; t < 9; ++t)
-        if (m < M && (unsigned)(py + t / 3 - 1) < (unsigned)s.H &&
-            (unsigned)(px + t % 3 - 1) < (unsigned)s.W)
-          mask[i] |= 1 << t;
-    }
+    for (int i = 0; i < TM; ++i) mask[i] = halo_mask(s, m0 + wm * (BM / 2) + 32 * i + r, M);
   }
   f32x16 acc[TM];
 #pragma unroll
@@ -342,7 +305,7 @@ X3_KERNEL void x3conv_kernel(const ConvShape s, const uint16_t* __restrict__ x,
 // values a thread from two 16-byte loads into one 16-byte store a plane (the lo
 // plane starts 2 n bytes in: for n % 8 != 0 its stores are scalar), the n % 8
 // tail by the first threads of block 0.
-X3_KERNEL void split_kernel(const float* __restrict__ x, long long n, uint16_t* __restrict__ out) {
+LOWP_KERNEL(NT) void split_kernel(const float* __restrict__ x, long long n, uint16_t* __restrict__ out) {
   const long long n8 = n / 8, stride = (long long)gridDim.x * NT;
   const bool lo16 = n % 8 == 0;
   for (long long i = (long long)blockIdx.x * NT + threadIdx.x; i < n8; i += stride) {
@@ -378,7 +341,7 @@ X3_KERNEL void split_kernel(const float* __restrict__ x, long long n, uint16_t* 
 // a job, first blocks ascending.  A block owns 32 output channels and walks
 // their slice 32 x 32 at a time through an LDS transpose, c contiguous on the
 // way out, into both planes.
-X3_KERNEL void wsplit_kernel(const long long* __restrict__ jobs, int njobs) {
+LOWP_KERNEL(NT) void wsplit_kernel(const long long* __restrict__ jobs, int njobs) {
   __shared__ float t[32][33];
   const int b = blockIdx.x;
   int j = 0;
@@ -414,7 +377,7 @@ X3_KERNEL void wsplit_kernel(const long long* __restrict__ jobs, int njobs) {
 // layouts are theirs): one thread per s2d pixel (n, Y, X) of [N][Hs][Ws],
 // channels (p * 2 + q) * 3 + ci = x[n][2 (Y - 2) + p][2 (X - 2) + q][ci] (zero
 // outside the image), 4 zero channels; two 16-byte stores a plane.
-X3_KERNEL void s2d_input_kernel(const float* __restrict__ x, int N, int H, int W, int Hs, int Ws,
+LOWP_KERNEL(NT) void s2d_input_kernel(const float* __restrict__ x, int N, int H, int W, int Hs, int Ws,
                                 uint4* __restrict__ xs) {
   const long long n_pix = (long long)N * Hs * Ws;
   for (long long i = (long long)blockIdx.x * NT + threadIdx.x; i < n_pix;
@@ -458,7 +421,7 @@ X3_KERNEL void s2d_input_kernel(const float* __restrict__ x, int N, int H, int W
 // wt8 planes [2][co][k], k = (a * 4 + b) * 16 + (p * 2 + q) * 3 + ci  <-
 // w[2a + p - 1][2b + q - 1][ci][co] (zero off the 7x7 kernel and on the 4
 // padding channels)
-X3_KERNEL void s2d_weight_kernel(const float* __restrict__ w, int K, uint16_t* __restrict__ wt8) {
+LOWP_KERNEL(NT) void s2d_weight_kernel(const float* __restrict__ w, int K, uint16_t* __restrict__ wt8) {
   const int n = K * 256;
   for (int i = blockIdx.x * NT + threadIdx.x; i < n; i += gridDim.x * NT) {
     const int co = i >> 8, k = i & 255, tap = k >> 4, ch = k & 15;
@@ -474,16 +437,10 @@ X3_KERNEL void s2d_weight_kernel(const float* __restrict__ w, int K, uint16_t* _
 template <int BM, int MODE>
 static void launch(const ConvShape& s, const void* x, const void* w, const X3Epi& e, void* y,
                    hipStream_t st) {
-  const int M = s.N * s.OH * s.OW;
-  const dim3 grid((unsigned)(((M + BM - 1) / BM) * (s.K / BN)));
-  x3conv_kernel<BM, MODE><<<grid, NT, 0, st>>>(s, reinterpret_cast<const uint16_t*>(x),
-                                               reinterpret_cast<const uint16_t*>(w), e,
-                                               reinterpret_cast<uint16_t*>(y));
+  x3conv_kernel<BM, MODE><<<conv_grid(s, BM), NT, 0, st>>>(
+      s, reinterpret_cast<const uint16_t*>(x), reinterpret_cast<const uint16_t*>(w), e,
+      reinterpret_cast<uint16_t*>(y));
 }
-
-#undef X3_KERNEL
-#undef X3_DEV
-#undef X3_TARGET
 
 static inline int grid1d(long long n) {
   const long long b = (n + NT - 1) / NT;
@@ -494,10 +451,6 @@ static inline int grid1d(long long n) {
 
 static bool x3_stem_shape(const ConvShape& s) {
   return s.R == 4 && s.S == 4 && s.C == 16 && s.stride == 1 && s.pad == 0;
-}
-
-static bool x3_halo_ok(const ConvShape& s, int bm) {
-  return s.R == 3 && s.S == 3 && s.stride == 1 && s.pad == 1 && bm + 2 * s.W + 2 <= cx3::HCAP;
 }
 
 bool x3conv_ok(const ConvShape& s) {
@@ -521,11 +474,11 @@ X3Plan x3conv_plan(const ConvShape& s, int form) {
   // of them exist; below that, 64-row tiles for the blocks
   p.bm = M >= 128 * 64 ? 128 : 64;
   const bool stem = x3_stem_shape(s);
-  p.form = form ? form : stem ? 3 : x3_halo_ok(s, p.bm) ? 2 : 1;
+  p.form = form ? form : stem ? 3 : lowp::halo_ok(s, p.bm) ? 2 : 1;
   if ((p.form == 3) != stem)
     throw std::runtime_error("x3conv: the stem form takes the 4x4 / stride 1 / pad 0 conv over 16 "
                              "channels, and that conv takes no other form");
-  if (p.form == 2 && !x3_halo_ok(s, p.bm))
+  if (p.form == 2 && !lowp::halo_ok(s, p.bm))
     throw std::runtime_error("x3conv: the halo form takes 3x3 / stride 1 / pad 1 with "
                              "bm + 2 W + 2 <= 248");
   return p;

@@ -87,6 +87,32 @@ void conv(const ConvShape& s, const void* x, uintptr_t wt, const ResnetInferPtrs
                              fold + off, fold + p.fold_total + off, res, relu, y, ws, st);
 }
 
+// The 19 convs of the eight residual blocks in launch order (a down block: ds,
+// c1, c2), on the three rotating buffers: conv(shape, in, out, i, res, relu,
+// last), i the conv's place in the weight order (a block's c1, c2, ds; its
+// BatchNorm is 1 + i), last set for the final block output.  Returns the index
+// of the buffer that holds that output.
+template <class F>
+int walk_blocks(const Net& n, void* const (&act)[3], F conv) {
+  int h = 1, t = 0, u = 2;  // the block input, c1's output, the shortcut / the next input
+  size_t wi = 0;
+  for (const Block& b : n.blocks) {
+    const bool last = &b == &n.blocks[7];
+    if (b.down) {
+      conv(b.ds, act[h], act[u], wi + 2, nullptr, false, false);
+      conv(b.c1, act[h], act[t], wi, nullptr, true, false);
+      conv(b.c2, act[t], act[h], wi + 1, act[u], true, last);
+      wi += 3;
+    } else {
+      conv(b.c1, act[h], act[t], wi, nullptr, true, false);
+      conv(b.c2, act[t], act[u], wi + 1, act[h], true, last);
+      std::swap(h, u);
+      wi += 2;
+    }
+  }
+  return h;
+}
+
 }  // namespace
 
 int ResnetInfer::max_rows(const ResnetInferPtrs& p) {
@@ -148,27 +174,11 @@ void run_bf16(const ResnetInferPtrs& p, uintptr_t x, int m, uintptr_t act0, uint
                                       fold + p.fold_total + p.fold_off[0], true, act[0], s);
   gops::maxpool_infer_b16(n.pool, act[0], act[1], s);
   seen(act[1], (long long)m * n.pool.OH * n.pool.OW * 64, 0);
-  int h = 1, t = 0, u = 2;  // the block input, c1's output, the shortcut / the next input
-  size_t wi = 0;
-  int bn = 1;
-  for (const Block& b : n.blocks) {
-    if (b.down) {
-      conv(b.ds, act[h], p.wt[wi + 2], p, bn + 2, nullptr, false, act[u], wsf, s);
-      seen(act[u], out_elems(b.ds), 1 + wi + 2);
-      conv(b.c1, act[h], p.wt[wi], p, bn, nullptr, true, act[t], wsf, s);
-      seen(act[t], out_elems(b.c1), 1 + wi);
-      conv(b.c2, act[t], p.wt[wi + 1], p, bn + 1, act[u], true, act[h], wsf, s);
-      seen(act[h], out_elems(b.c2), 1 + wi + 1);
-      wi += 3, bn += 3;
-    } else {
-      conv(b.c1, act[h], p.wt[wi], p, bn, nullptr, true, act[t], wsf, s);
-      seen(act[t], out_elems(b.c1), 1 + wi);
-      conv(b.c2, act[t], p.wt[wi + 1], p, bn + 1, act[h], true, act[u], wsf, s);
-      seen(act[u], out_elems(b.c2), 1 + wi + 1);
-      std::swap(h, u);
-      wi += 2, bn += 2;
-    }
-  }
+  const int h = walk_blocks(n, act, [&](const ConvShape& cs, const void* in, void* out, size_t i,
+                                        const void* res, bool relu, bool) {
+    conv(cs, in, p.wt[i], p, 1 + (int)i, res, relu, out, wsf, s);
+    seen(out, out_elems(cs), 1 + i);
+  });
   gops::avgpool_fc(act[h], P<const float>(p.fc_w), P<const float>(p.fc_b), P<float>(logits), m,
                    n.fh * n.fw, 512, p.classes, s);
 }
@@ -211,8 +221,9 @@ void ResnetInfer::eval_chunk_f8(const ResnetInferPtrs& p, uintptr_t x, int m, ui
                                       fold + p.fold_total + p.fold_off[0], true, act[0], s);
   gops::maxpool_infer_f8(n.pool, act[0], scal + 2 * 19, act[1], s);
   // conv i of the weight order: BatchNorm 1 + i, scales scal[i] / scal[19 + i]
-  auto conv8 = [&](const ConvShape& cs, const void* xin, size_t i, const void* res, bool relu,
-                   void* y, bool last) {
+  // (the final block output stays bf16 for avgpool_fc)
+  auto conv8 = [&](const ConvShape& cs, const void* xin, void* y, size_t i, const void* res,
+                   bool relu, bool last) {
     gops::F8Epi e;
     const int off = p.fold_off[1 + i];
     e.a2 = a2 + off, e.b = fold + p.fold_total + off;
@@ -222,22 +233,7 @@ void ResnetInfer::eval_chunk_f8(const ResnetInferPtrs& p, uintptr_t x, int m, ui
     else
       gops::f8conv(cs, xin, P<const void>(p.w8[i]), e, y, last, 0, 0, s);
   };
-  int h = 1, t = 0, u = 2;
-  size_t wi = 0;
-  for (const Block& b : n.blocks) {
-    const bool last = &b == &n.blocks[7];  // the final block output stays bf16 for avgpool_fc
-    if (b.down) {
-      conv8(b.ds, act[h], wi + 2, nullptr, false, act[u], false);
-      conv8(b.c1, act[h], wi, nullptr, true, act[t], false);
-      conv8(b.c2, act[t], wi + 1, act[u], true, act[h], last);
-      wi += 3;
-    } else {
-      conv8(b.c1, act[h], wi, nullptr, true, act[t], false);
-      conv8(b.c2, act[t], wi + 1, act[h], true, act[u], last);
-      std::swap(h, u);
-      wi += 2;
-    }
-  }
+  const int h = walk_blocks(n, act, conv8);
   gops::avgpool_fc(act[h], P<const float>(p.fc_w), P<const float>(p.fc_b), P<float>(logits), m,
                    n.fh * n.fw, 512, p.classes, s);
 }
@@ -254,33 +250,21 @@ void ResnetInfer::eval_chunk_x3(const ResnetInferPtrs& p, uintptr_t x, int m, ui
   const Net n(p, m);
   void* act[3] = {P<void>(act0), P<void>(act1), P<void>(act2)};
   const float* fold = P<const float>(p.fold);
-  // conv i of the weight order runs BatchNorm 1 + i; bn 0 is the stem's
-  auto conv3 = [&](const ConvShape& cs, const void* xin, uintptr_t w, int bn, const void* res,
-                   bool relu, void* y) {
+  // BatchNorm bn: 0 the stem's, 1 + i conv i's of the weight order
+  auto conv3 = [&](const ConvShape& cs, const void* xin, void* y, uintptr_t w, int bn,
+                   const void* res, bool relu) {
     gops::X3Epi e;
     const int off = p.fold_off[bn];
     e.a = fold + off, e.b = fold + p.fold_total + off, e.res = res, e.relu = relu ? 1 : 0;
     gops::x3conv(cs, xin, P<const void>(w), e, y, 0, s);
   };
   gops::s2d_stem_input_x3(P<const float>(x), m, p.H, p.W, n.stem.OH, n.stem.OW, act[1], s);
-  conv3(n.s2d, act[1], p.wt8x3, 0, nullptr, true, act[0]);
+  conv3(n.s2d, act[1], act[0], p.wt8x3, 0, nullptr, true);
   gops::maxpool_infer_x3(n.pool, act[0], act[1], s);
-  int h = 1, t = 0, u = 2;  // as run_bf16
-  size_t wi = 0;
-  for (const Block& b : n.blocks) {
-    const int bn = 1 + (int)wi;
-    if (b.down) {
-      conv3(b.ds, act[h], p.wx3[wi + 2], bn + 2, nullptr, false, act[u]);
-      conv3(b.c1, act[h], p.wx3[wi], bn, nullptr, true, act[t]);
-      conv3(b.c2, act[t], p.wx3[wi + 1], bn + 1, act[u], true, act[h]);
-      wi += 3;
-    } else {
-      conv3(b.c1, act[h], p.wx3[wi], bn, nullptr, true, act[t]);
-      conv3(b.c2, act[t], p.wx3[wi + 1], bn + 1, act[h], true, act[u]);
-      std::swap(h, u);
-      wi += 2;
-    }
-  }
+  const int h = walk_blocks(n, act, [&](const ConvShape& cs, const void* in, void* out, size_t i,
+                                        const void* res, bool relu, bool) {
+    conv3(cs, in, out, p.wx3[i], 1 + (int)i, res, relu);
+  });
   gops::avgpool_fc_x3(act[h], P<const float>(p.fc_w), P<const float>(p.fc_b), P<float>(logits), m,
                       n.fh * n.fw, 512, p.classes, s);
 }

@@ -2,38 +2,24 @@
 against the host packer, Predictor against the emulation of helpers/resnet_mx4_ref.py."""
 
 import functools
-import importlib.util
-import os
 
 import numpy as np
 import pytest
 import torch
+from helpers import lowp_conv as L
 
 from mpi_tensorflow_amd.ops import native, ptr, stream_handle
 
 pytestmark = pytest.mark.gpu
 
-
-def _load(name):
-    spec = importlib.util.spec_from_file_location(
-        name, os.path.join(os.path.dirname(os.path.abspath(__file__)), "helpers", name + ".py"))
-    mod = importlib.util.module_from_spec(spec)
-    spec.loader.exec_module(mod)
-    return mod
-
-
-R, H_, X = _load("conv_ref"), _load("resnet_state"), _load("resnet_mx4_ref")
-E8, F64, BF, F8 = X.E8, torch.float64, torch.bfloat16, torch.float8_e4m3fn
+R, H_, X = L.R, L.load("resnet_state"), L.load("resnet_mx4_ref")
+E8, F64, BF, F8 = X.E8, L.F64, L.BF, L.F8
 # test_resnet_fp8_gpu.py's five (deepest K; ragged M, three column tiles; the 128-row tile; 3x3
 # stride 2; 1x1 stride 2) and a two-chunk halo shape: the single-buffered slab is staged again
 SHAPES = [(3, 7, 7, 512, 512, 3, 1, 1), (3, 11, 13, 64, 192, 3, 1, 1), (11, 56, 56, 64, 64, 3, 1, 1),
           (2, 14, 14, 64, 128, 3, 2, 1), (4, 14, 14, 128, 64, 1, 2, 0), (2, 9, 9, 128, 64, 3, 1, 1)]
 RUNS = [(s, f) for s in SHAPES for f in ((1, 2) if s[5] == 3 and s[6] == 1 else (1,))]
 IDS = ["x".join(map(str, s)) + f"-form{f}" for s, f in RUNS]
-
-
-def codes(t, dev):  # e4m3-exact values -> their codes, uploaded as bytes
-    return t.to(torch.float32).to(F8).view(torch.uint8).to(dev)
 
 
 def slabs(w):  # MX-exact weights -> the host packer's bytes
@@ -58,29 +44,14 @@ def exact_ops(shape):
 @functools.lru_cache(maxsize=None)
 def epilogue_ops(shape):
     """test_resnet_fp8_gpu.py's epilogue operands with random MX-exact weights."""
-    N, H, W, C, K, Rr, stride, pad = shape
-    g = torch.Generator().manual_seed(900 + SHAPES.index(shape))
-    x = E8.q(torch.randn(N, H, W, C, generator=g).to(F64) * 2)
-    w = X.mx4_dequant(*X.mx4_quantise(torch.randn(Rr, Rr, C, K, generator=g) * 8 * (Rr * Rr * C) ** -0.5))
-    a2 = (torch.rand(K, generator=g) * 1.5 + 0.5) * (torch.randint(0, 2, (K,), generator=g) * 2 - 1) / 16
-    b = torch.rand(K, generator=g) * 2 - 1
-    ref = R.conv_fwd(x, w, stride, pad)
-    return x, slabs(w), a2, b, E8.q(torch.randn(ref[0].shape, generator=g).to(F64) * 4), 0.5, ref
+    x, w, *rest = L.epilogue_ops(shape, 900 + SHAPES.index(shape), E8.q,
+                                 lambda r, n: X.mx4_dequant(*X.mx4_quantise(r * 8 * n ** -0.5)))
+    return (x, slabs(w), *rest)
 
 
 def run_mx4conv(dev, shape, x, w, a2, b, res, s_res, inv, relu, out_bf16, form, canary):
-    ops, (N, H, W, C, K, Rr, stride, pad) = native().ops, shape
-    sh = ops.ConvShape(N, H, W, C, K, Rr, Rr, stride, pad)
-    M = N * sh.OH * sh.OW
-    y = torch.full((M * K + 4096,), canary, dtype=BF if out_bf16 else torch.uint8, device=dev)
-    t = [codes(x, dev), w.to(dev), a2.to(dev), b.to(dev), codes(res, dev) if res is not None else None,
-         torch.tensor([s_res, inv], dtype=torch.float32, device=dev)]
-    ops.mx4conv(sh, ptr(t[0]), ptr(t[1]), ptr(t[2]), ptr(t[3]), ptr(t[4]), ptr(t[5]), ptr(t[5]) + 4,
-                relu, ptr(y), out_bf16, stream_handle(), form=form)
-    torch.cuda.synchronize()
-    got = y.cpu()
-    assert R.guard_hits(got.float() if out_bf16 else got, M * K, canary) == 0
-    return got[:M * K].reshape(N, sh.OH, sh.OW, K), ops.mx4conv_plan(sh, form)
+    return L.run_byte_conv("mx4conv", dev, shape, x, w, a2, b, res, s_res, inv, relu, out_bf16, canary,
+                           form=form)
 
 
 @pytest.mark.parametrize("shape,form", RUNS, ids=IDS)

@@ -3,31 +3,20 @@ float64 and exactly, the small kernels against torch, Predictor against float64 
 End to end on 3 rows, max |logits - fp64|: the figures are in docs/ACCURACY.md."""
 
 import functools
-import importlib.util
-import os
 
 import numpy as np
 import pytest
 import torch
 import torch.nn.functional as F
+from helpers import lowp_conv as L
 
 from mpi_tensorflow_amd.ops import functional as Fn
 from mpi_tensorflow_amd.ops import native, ptr, stream_handle
 
 pytestmark = pytest.mark.gpu
 
-_HERE = os.path.dirname(os.path.abspath(__file__))
-
-
-def _load(name):
-    spec = importlib.util.spec_from_file_location(name, os.path.join(_HERE, "helpers", name + ".py"))
-    mod = importlib.util.module_from_spec(spec)
-    spec.loader.exec_module(mod)
-    return mod
-
-
-R, H_ = _load("conv_ref"), _load("resnet_state")
-F64, BF = torch.float64, torch.bfloat16
+R, H_ = L.R, L.load("resnet_state")
+F64, BF = L.F64, L.BF
 # (N, H, W, C, K, R, stride, pad) -> (loader, bm) of ops.x3conv_route; the M rule is bm = 128
 # from M = 8192 (the 128-row gather and stem tiles are the two cases with M = 8624 and 9408)
 CASES = [((4, 14, 14, 64, 64, 3, 1, 1), ("halo", 64)), ((3, 56, 56, 64, 64, 3, 1, 1), ("halo", 128)),
@@ -71,9 +60,7 @@ def run_x3conv(dev, shape, route, x, w, a, b, res, relu):
     y = torch.full((2 * M * K + 4096,), CANARY, dtype=BF, device=dev)
     t = [a.to(dev), b.to(dev), planes(res, dev) if res is not None else None]
     ops.x3conv(run, ptr(xp), ptr(wp), ptr(t[0]), ptr(t[1]), ptr(t[2]), relu, ptr(y), s)
-    torch.cuda.synchronize()
-    got = y.cpu()
-    assert R.guard_hits(got.float(), 2 * M * K, CANARY) == 0
+    got = L.checked(y, 2 * M * K, CANARY)
     return join(got, M * K, (N, sh.OH, sh.OW, K)), got
 
 
